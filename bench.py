@@ -8,6 +8,12 @@ of one node — rank-per-GPU data parallelism over RCCL.  One "step" = one
 generate() call of `--batch` images on every rank.  Rank 0 prints ONE JSON
 line with the whole-job aggregate images/sec.
 
+A plain run does only what that figure needs: set up, warm up, time the K
+steps, print the line.  `--dump-outputs DIR` also writes the images of the
+last timed step as float32 `.npy` (same arguments -> same inputs, so two
+builds can be compared output for output).  `--full` is where any further
+measurement belongs; the flagship benchmark has none today.
+
 Reference anchor: SD3.5-Large-Turbo/SDXL-class 1024px ≈ 0.5-1
 image/s on one H100 (text_to_image.py:11-13); vs_baseline divides by
 1.0 img/s × n_gpus (the reference's BEST case, scaled to node size).
@@ -21,6 +27,30 @@ import json
 import os
 import sys
 import time
+
+
+DUMP_CAP_BYTES = 48 << 20  # most that one --dump-outputs writes, all ranks
+
+
+def _dump_outputs(out_dir, images, rank, world):
+    """Write what generate() returned in the last timed step as float32.
+    An output over this rank's share of the cap is reduced to a fixed,
+    seeded sample of its flattened elements: those at the sorted indices
+    RandomState(0).randint(0, size, budget), the same in every run."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = "" if world == 1 else f"_rank{rank}"
+    flat = images.detach().cpu().numpy().reshape(-1)
+    budget = DUMP_CAP_BYTES // world // 4  # float32 elements
+    if flat.size > budget:
+        idx = np.sort(np.random.RandomState(0).randint(0, flat.size, budget))
+        flat = flat[idx]
+        name = f"images_sample{suffix}.npy"
+    else:
+        flat = flat.reshape(tuple(images.shape))
+        name = f"images{suffix}.npy"
+    np.save(os.path.join(out_dir, name), flat.astype(np.float32))
 
 
 def main():
@@ -37,7 +67,15 @@ def main():
     ap.add_argument("--latent", type=int, default=128, help="128 → 1024px")
     ap.add_argument("--small", action="store_true", help="test-size model")
     ap.add_argument("--no-graph", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's images to DIR/<name>.npy "
+                         "(float32; a fixed seeded sample when over the cap)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline "
+                         "figure (none for this benchmark today)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
 
@@ -82,7 +120,7 @@ def main():
         dist.barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        one_step()
+        last = one_step()
     if torch.cuda.is_available():
         torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
@@ -93,6 +131,9 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
         dist.barrier()
+
+    if args.dump_outputs:
+        _dump_outputs(args.dump_outputs, last, rank, world)
 
     n_gpus = world if dist_on else (1 if torch.cuda.is_available() else args.gpus or 1)
     total_images = args.steps * args.batch * (world if dist_on else 1)

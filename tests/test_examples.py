@@ -89,19 +89,52 @@ def test_example_runs_end_to_end(stem):
     assert r.returncode == 0, f"{stem} failed:\n{r.stdout[-2000:]}\n{r.stderr[-2000:]}"
 
 
-def test_diff_matrix_tool():
+def test_diff_matrix_tool(tmp_path):
     """tools/generate_diff_matrix.py: diff-driven CI fan-out (reference
     internal/generate_diff_matrix.py role) emits valid JSON and flags
-    runtime-wide changes."""
+    runtime-wide changes.  Runs on a scratch git repository holding a copy of
+    tools/ and examples/, so it needs no history of the checkout it is in
+    (a shallow or exported tree has no HEAD~3)."""
     import json
+    import shutil
 
-    r = subprocess.run(
-        [sys.executable, str(REPO / "tools" / "generate_diff_matrix.py"),
-         "HEAD~3"],
-        capture_output=True, text=True, cwd=REPO, timeout=60)
-    assert r.returncode == 0, r.stderr[-1000:]
-    out = json.loads(r.stdout)
-    assert set(out) == {"runtime_changed", "examples"}
-    assert isinstance(out["examples"], list)
-    if out["runtime_changed"]:  # runtime edits fan out to every example
-        assert len(out["examples"]) == len(EXAMPLES)
+    work = tmp_path / "repo"
+    shutil.copytree(REPO / "tools", work / "tools",
+                    ignore=shutil.ignore_patterns("__pycache__"))
+    shutil.copytree(REPO / "examples", work / "examples",
+                    ignore=shutil.ignore_patterns("__pycache__"))
+
+    def git(*args):
+        r = subprocess.run(
+            ["git", "-c", "user.name=t", "-c", "user.email=t@example.com",
+             *args], capture_output=True, text=True, cwd=work, timeout=60)
+        assert r.returncode == 0, r.stderr[-1000:]
+
+    def matrix(base):
+        r = subprocess.run(
+            [sys.executable, str(work / "tools" / "generate_diff_matrix.py"),
+             base],
+            capture_output=True, text=True, cwd=work, timeout=60)
+        assert r.returncode == 0, r.stderr[-1000:]
+        out = json.loads(r.stdout)
+        assert set(out) == {"runtime_changed", "examples"}
+        assert isinstance(out["examples"], list)
+        return out
+
+    git("init", "-q")
+    git("add", "-A")
+    git("commit", "-q", "-m", "base")
+    hello = next(e for e in EXAMPLES if e.stem == "hello_world")
+    with open(work / hello.path.relative_to(REPO), "a") as f:
+        f.write("\n# touched\n")
+    git("commit", "-q", "-am", "touch one example")
+    out = matrix("HEAD~1")
+    assert not out["runtime_changed"]
+    assert out["examples"] == ["hello_world"]
+
+    with open(work / "tools" / "example_utils.py", "a") as f:
+        f.write("\n# touched\n")
+    git("commit", "-q", "-am", "touch the runtime")
+    out = matrix("HEAD~1")
+    assert out["runtime_changed"]  # runtime edits fan out to every example
+    assert len(out["examples"]) == len(EXAMPLES)

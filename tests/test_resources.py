@@ -8,6 +8,25 @@ import pytest
 import modal_examples_amd as modal
 
 
+def _require_mount_namespace():
+    """Read-only bind mounts need a private mount namespace: CAP_SYS_ADMIN,
+    or a kernel that lets this user create user namespaces.  Asked of the
+    kernel in a throwaway child, before the test does any work."""
+    import subprocess
+    import sys
+
+    probe = (
+        "import ctypes, sys\n"
+        "libc = ctypes.CDLL('libc.so.6', use_errno=True)\n"
+        "ok = libc.unshare(0x00020000) == 0 or "
+        "libc.unshare(0x10000000 | 0x00020000) == 0\n"
+        "sys.exit(0 if ok else 1)\n")
+    if subprocess.run([sys.executable, "-c", probe], timeout=60).returncode != 0:
+        pytest.skip("needs a private mount namespace: this user has neither "
+                    "CAP_SYS_ADMIN nor permission to create user namespaces "
+                    "(user.max_user_namespaces is 0 or the kernel denies it)")
+
+
 def test_volume_write_read_across_processes():
     vol = modal.Volume.from_name("test-vol", create_if_missing=True)
     app = modal.App("test-vol-app")
@@ -212,6 +231,7 @@ def test_volume_read_only_mount_enforced_in_worker():
     """A read-only mount is a ro bind mount in the worker's private mount
     namespace: raw file writes fail with EROFS, reads work, and the parent
     namespace (this process) never sees the mount."""
+    _require_mount_namespace()
     vol = modal.Volume.from_name("ro-mount-vol", create_if_missing=True)
     (vol.path / "probe.txt").write_text("ro-mounted")
     app = modal.App("test-ro-mount-app")
@@ -337,7 +357,8 @@ def test_period_schedule_fires_live():
 def test_bucket_mount_read_only():
     """CloudBucketMount(read_only=True) gets the same filesystem-level
     enforcement as Volume.read_only() (ro bind mount in the worker)."""
-    bucket = modal.CloudBucketMount("models-bucket", read_only=True)
+    _require_mount_namespace()
+    bucket =modal.CloudBucketMount("models-bucket", read_only=True)
     # pre-populate the local bucket dir
     (bucket.path / "weights.txt").write_text("frozen")
     app_b = modal.App("test-bucket-ro")
@@ -438,12 +459,15 @@ def test_bucket_mount_prefix_sync_and_writeback(tmp_path):
     app = modal.App("test-s3-mount")
     mnt = modal.CloudBucketMount("sync-bkt", key_prefix="data")
 
-    @app.function(volumes={"/mnt/bkt": mnt}, scaledown_window=0.5)
+    # a mount point any user can create, unlike one under /mnt
+    mount_path = str(tmp_path / "bkt")
+
+    @app.function(volumes={mount_path: mnt}, scaledown_window=0.5)
     def roundtrip() -> dict:
         import os
         from pathlib import Path
 
-        p = Path("/mnt/bkt")
+        p = Path(mount_path)
         seen = sorted(f.name for f in p.glob("**/*") if f.is_file())
         (p / "out.txt").write_text("produced")
         real = os.path.realpath(p)

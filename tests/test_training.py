@@ -140,6 +140,8 @@ def _trainer_ddp_worker(rank, world, port, results):
     os.environ.update({
         "RANK": str(rank), "WORLD_SIZE": str(world), "LOCAL_RANK": str(rank),
         "MASTER_ADDR": "127.0.0.1", "MASTER_PORT": str(port),
+        # a CPU trainer: keep init_distributed() on gloo where GPUs exist
+        "HIP_VISIBLE_DEVICES": "", "CUDA_VISIBLE_DEVICES": "",
     })
     t = LoRATrainer(
         UNetConfig.small(),
