@@ -20,7 +20,6 @@ SO_PATH = OPS_DIR / "_hip_ops.so"
 ARCH = os.environ.get("PYTORCH_ROCM_ARCH", "gfx950")
 
 HIP_SOURCES = [
-    "attention_fwd.hip",
     "attention_fwd32.hip",
     "attention_decode.hip",
     "norms.hip",

@@ -23,7 +23,6 @@
 // cache (then block_size must be >= max seq len).
 #include "common.h"
 
-#include <cstdio>
 #include <type_traits>
 
 #define DEC_THREADS 256
@@ -249,16 +248,17 @@ __global__ __launch_bounds__(256) void decode_merge_kernel(
   }
 }
 
-extern "C" void paged_decode_bf16(const void* q, const void* kc, const void* vc,
-                                  const int* block_table, const int* seq_lens,
-                                  void* o, float* ws, int B, int Hq, int Hkv,
-                                  int D, int block_size, int max_blocks,
-                                  int splits, float scale, int kv_fp8,
-                                  hipStream_t stream) {
-  if (Hq / Hkv > MAX_G) {
-    fprintf(stderr, "paged_decode_bf16: GQA group %d > %d\n", Hq / Hkv, MAX_G);
-    abort();
-  }
+// Returns 0 once the kernels are launched, non-zero (nothing launched) for an
+// unsupported configuration: D must be 64 or 128, Hq a multiple of Hkv and
+// the GQA group Hq/Hkv at most MAX_G.
+extern "C" int paged_decode_bf16(const void* q, const void* kc, const void* vc,
+                                 const int* block_table, const int* seq_lens,
+                                 void* o, float* ws, int B, int Hq, int Hkv,
+                                 int D, int block_size, int max_blocks,
+                                 int splits, float scale, int kv_fp8,
+                                 hipStream_t stream) {
+  if ((D != 64 && D != 128) || Hkv <= 0 || Hq % Hkv != 0 || Hq / Hkv > MAX_G)
+    return 1;
   if (splits < 1) splits = 1;
   dim3 grid(Hkv, B, splits);
   dim3 block(DEC_THREADS);
@@ -283,11 +283,8 @@ extern "C" void paged_decode_bf16(const void* q, const void* kc, const void* vc,
   } while (0)
   if (D == 64) {
     DDISPATCH(64);
-  } else if (D == 128) {
-    DDISPATCH(128);
   } else {
-    fprintf(stderr, "paged_decode_bf16: unsupported head_dim %d\n", D);
-    abort();
+    DDISPATCH(128);
   }
 #undef DDISPATCH
 #undef DGROUP
@@ -296,4 +293,5 @@ extern "C" void paged_decode_bf16(const void* q, const void* kc, const void* vc,
     hipLaunchKernelGGL(decode_merge_kernel, dim3(B * Hq), dim3(256), 0,
                        stream, ws, (short*)o, B, Hq, D, splits);
   }
+  return 0;
 }

@@ -1,6 +1,8 @@
-// Flash-attention forward v7 — 32x32x16 MFMA with LANE-LOCAL online softmax.
+// Flash-attention forward v8 — 32x32x16 MFMA with LANE-LOCAL online softmax,
+// per-head-dim KV block size and defer-max rescale skipping.  The single
+// forward attention kernel: every model reaches it through bindings.cpp.
 //
-// The v3-v6 kernels (attention_fwd.hip) are softmax-LATENCY-bound: ablation
+// The retired 16x16 kernels (v3-v6) were softmax-LATENCY-bound: ablation
 // measured the 16-lane-group shuffle/exp chains at ~56% of kernel time.  This
 // structure eliminates cross-lane reductions almost entirely (the m214-style
 // swapped-operand recipe, re-derived for gfx950):
@@ -21,7 +23,6 @@
 //   C[m][n]: lane holds C[(reg&3)+8*(reg>>2)+4*(l>>5)][l&31], reg 0..15.
 #include "common.h"
 
-#include <cstdio>
 #include <cstdlib>
 
 #define FA32_NWAVES 4
@@ -85,23 +86,17 @@ __global__ __launch_bounds__(FA32_NWAVES * WAVE) void fa32_kernel(
   const int my_q = q0 + l31;  // this lane's query row
   const int causal_off = Sk - Sq;
 
-  // Q^T B-fragments: qreg[c][j] = Q[my_q][c*16 + hi5*8 + j].
-  // D=128 would spend 32 VGPR on Q (dropping occupancy to 2 waves/SIMD);
-  // since Q is re-read once per KV block and stays L2-resident, the large-D
-  // path reloads fragments from global inside the QK loop instead.
-  // measured: reloading Q from L2 regressed D=128 22-30% (occupancy stayed
-  // at 2 waves; the extra global traffic was pure cost) — registers for all D
-  constexpr bool QREG = true;
-  bf16x8 qreg[QREG ? DCH : 1];
+  // Q^T B-fragments: qreg[c][j] = Q[my_q][c*16 + hi5*8 + j], held in
+  // registers for all D — measured: reloading Q from L2 per KV block instead
+  // regressed D=128 by 22-30% (occupancy stayed at 2 waves/SIMD).
+  bf16x8 qreg[DCH];
   const long long qrow_off = qoff + (long long)my_q * st.qs;
   const bool q_ok = my_q < Sq;
-  if (QREG) {
 #pragma unroll
-    for (int c = 0; c < (QREG ? DCH : 1); ++c) {
-      qreg[c] = q_ok
-          ? *(const bf16x8*)&Q[qrow_off + c * 16 + hi5 * 8]
-          : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-    }
+  for (int c = 0; c < DCH; ++c) {
+    qreg[c] = q_ok
+        ? *(const bf16x8*)&Q[qrow_off + c * 16 + hi5 * 8]
+        : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
   }
 
   f32x16 acc[DT];
@@ -169,15 +164,9 @@ __global__ __launch_bounds__(FA32_NWAVES * WAVE) void fa32_kernel(
         int krow = f * 32 + l31;
         bf16x8 kfrag = *(const bf16x8*)(
             (char*)&Ks[krow][0] + kv_swz7(krow, (c * 16 + hi5 * 8) * 2));
-        bf16x8 qf;
-        if (QREG) {
-          qf = qreg[c % (QREG ? DCH : 1)];
-        } else {
-          qf = q_ok ? *(const bf16x8*)&Q[qrow_off + c * 16 + hi5 * 8]
-                    : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-        }
         __builtin_amdgcn_s_setprio(1);
-        s[f] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfrag, qf, s[f], 0, 0, 0);
+        s[f] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfrag, qreg[c], s[f], 0,
+                                                       0, 0);
         __builtin_amdgcn_s_setprio(0);
       }
     }
@@ -288,10 +277,15 @@ __global__ __launch_bounds__(FA32_NWAVES * WAVE) void fa32_kernel(
   }
 }
 
-extern "C" void fa32_fwd_strided_bf16(
+// q/k/v/o are logically [B,H,S,D] with d contiguous; strides[12] holds the
+// element strides qb qh qs kb kh ks vb vh vs ob oh os.  Returns 0 once the
+// kernel is launched, non-zero (nothing launched) for an unsupported
+// configuration: D must be 64 or 128 and Hq a multiple of Hkv.
+extern "C" int fa32_fwd_strided_bf16(
     const void* q, const void* k, const void* v, void* o, int B, int Hq,
     int Hkv, int Sq, int Sk, int D, float scale, int causal,
     const long long* strides, hipStream_t stream) {
+  if ((D != 64 && D != 128) || Hkv <= 0 || Hq % Hkv != 0) return 1;
   const short* Qp = (const short*)q;
   const short* Kp = (const short*)k;
   const short* Vp = (const short*)v;
@@ -320,11 +314,9 @@ extern "C" void fa32_fwd_strided_bf16(
   } while (0)
   if (D == 64) {
     if (causal) L32K(64, true, 64); else L32K(64, false, 64);
-  } else if (D == 128) {
-    if (causal) L32K(128, true, 32); else L32K(128, false, 32);
   } else {
-    fprintf(stderr, "fa32: unsupported head_dim %d\n", D);
-    abort();
+    if (causal) L32K(128, true, 32); else L32K(128, false, 32);
   }
 #undef L32K
+  return 0;
 }

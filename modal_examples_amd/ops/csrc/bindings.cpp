@@ -14,14 +14,14 @@
 
 // ---- extern "C" launchers from the .hip translation units ----
 extern "C" {
-void fa_fwd_bf16(const void*, const void*, const void*, void*, int, int, int,
-                 int, int, int, float, int, hipStream_t);
-void fa_fwd_strided_bf16(const void*, const void*, const void*, void*, int,
-                         int, int, int, int, int, float, int,
-                         const long long*, hipStream_t);
-void paged_decode_bf16(const void*, const void*, const void*, const int*,
-                       const int*, void*, float*, int, int, int, int, int,
-                       int, int, float, int, hipStream_t);
+// the two attention launchers return 0 once launched, non-zero (nothing
+// launched) for a configuration they do not support
+int fa32_fwd_strided_bf16(const void*, const void*, const void*, void*, int,
+                          int, int, int, int, int, float, int,
+                          const long long*, hipStream_t);
+int paged_decode_bf16(const void*, const void*, const void*, const int*,
+                      const int*, void*, float*, int, int, int, int, int,
+                      int, int, float, int, hipStream_t);
 void groupnorm_silu_bf16(const void*, void*, float*, const float*,
                          const float*, int, int, long long, int, float, int,
                          hipStream_t);
@@ -43,7 +43,6 @@ void adamw_step(void*, const void*, float*, float*, long long, float, float,
 void gumbel_sample(const float*, unsigned long long*, int*, int, int,
                    float, unsigned long long, hipStream_t);
 void softmax_rows(const float*, float*, int, int, hipStream_t);
-void tr16_probe(short*, hipStream_t);
 void scale_in_dev_bf16(const void*, void*, const float*, const long long*,
                        long long, hipStream_t);
 void cfg_euler_dev_bf16(const void*, const void*, const void*, void*,
@@ -72,18 +71,52 @@ void check_bf16(const torch::Tensor& t, const char* name) {
 
 // ---------------------------------------------------------------- attention
 
+void check_bhsd(const torch::Tensor& t, const char* name) {
+  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
+  TORCH_CHECK(t.scalar_type() == torch::kBFloat16, name, " must be bf16");
+  TORCH_CHECK(t.dim() == 4, name, " must be [B,H,S,D]");
+  TORCH_CHECK(t.stride(3) == 1, name, ": head_dim must be contiguous");
+}
+
+// The one forward-attention launch: q/k/v/o are logically [B,H,S,D] with ANY
+// batch/head/sequence strides (d contiguous), read straight off the tensors.
+// Unsupported configurations raise here, before anything is launched.
+void attention_fwd(const torch::Tensor& q, const torch::Tensor& k,
+                   const torch::Tensor& v, const torch::Tensor& o, bool causal,
+                   double scale) {
+  check_bhsd(q, "q");
+  check_bhsd(k, "k");
+  check_bhsd(v, "v");
+  int B = q.size(0), Hq = q.size(1), Sq = q.size(2), D = q.size(3);
+  int Hkv = k.size(1), Sk = k.size(2);
+  TORCH_CHECK(D == 64 || D == 128, "attention: unsupported head_dim ", D,
+              " (supported: 64, 128)");
+  TORCH_CHECK(k.size(0) == B && k.size(3) == D && v.sizes() == k.sizes(),
+              "attention: k/v must be [B,Hkv,Sk,D] matching q's B and D");
+  TORCH_CHECK(Hkv > 0 && Hq % Hkv == 0, "GQA requires Hq % Hkv == 0, got Hq=",
+              Hq, " Hkv=", Hkv);
+  long long st[12] = {
+      q.stride(0), q.stride(1), q.stride(2),
+      k.stride(0), k.stride(1), k.stride(2),
+      v.stride(0), v.stride(1), v.stride(2),
+      o.stride(0), o.stride(1), o.stride(2),
+  };
+  int rc = fa32_fwd_strided_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                                 o.data_ptr(), B, Hq, Hkv, Sq, Sk, D,
+                                 (float)scale, causal ? 1 : 0, st,
+                                 cur_stream());
+  TORCH_CHECK(rc == 0, "attention: configuration not supported by the kernel "
+              "(head_dim must be 64 or 128 and Hq a multiple of Hkv; got D=",
+              D, " Hq=", Hq, " Hkv=", Hkv, ")");
+}
+
 torch::Tensor attention(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                         bool causal, double scale) {
   check_bf16(q, "q");
   check_bf16(k, "k");
   check_bf16(v, "v");
-  TORCH_CHECK(q.dim() == 4, "q must be [B,H,S,D]");
-  int B = q.size(0), Hq = q.size(1), Sq = q.size(2), D = q.size(3);
-  int Hkv = k.size(1), Sk = k.size(2);
-  TORCH_CHECK(Hq % Hkv == 0, "GQA requires Hq % Hkv == 0");
   auto o = torch::empty_like(q);
-  fa_fwd_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), B, Hq,
-              Hkv, Sq, Sk, D, (float)scale, causal ? 1 : 0, cur_stream());
+  attention_fwd(q, k, v, o, causal, scale);
   return o;
 }
 
@@ -99,15 +132,24 @@ torch::Tensor paged_decode(torch::Tensor q, torch::Tensor kc, torch::Tensor vc,
               "k_cache must be bf16 or float8_e4m3fn");
   TORCH_CHECK(vc.scalar_type() == kc.scalar_type(), "kv cache dtype mismatch");
   TORCH_CHECK(kc.is_contiguous() && vc.is_contiguous());
+  TORCH_CHECK(q.dim() == 3 && kc.dim() == 4, "q must be [B,Hq,D], k_cache "
+              "[blocks,Hkv,block_size,D] or [B,Hkv,S,D]");
   int B = q.size(0), Hq = q.size(1), D = q.size(2);
-  int Hkv, max_blocks = 0;
+  // cache is [blocks, Hkv, block_size, D], or [B, Hkv, S, D] without a table
+  int Hkv = kc.size(1), max_blocks = 0;
+  TORCH_CHECK(D == 64 || D == 128, "paged_decode: unsupported head_dim ", D,
+              " (supported: 64, 128)");
+  TORCH_CHECK(kc.size(3) == D, "paged_decode: k_cache head_dim ", kc.size(3),
+              " != q head_dim ", D);
+  TORCH_CHECK(Hkv > 0 && Hq % Hkv == 0, "GQA requires Hq % Hkv == 0, got Hq=",
+              Hq, " Hkv=", Hkv);
+  TORCH_CHECK(Hq / Hkv <= 8, "paged_decode: unsupported GQA group Hq/Hkv = ",
+              Hq / Hkv, " (supported: 1..8)");
   const int* bt_ptr = nullptr;
   if (block_table.has_value()) {
-    Hkv = kc.size(1);  // [blocks, Hkv, block_size, D]
     max_blocks = block_table->size(1);
     bt_ptr = block_table->data_ptr<int>();
   } else {
-    Hkv = kc.size(1);  // [B, Hkv, S, D]; block_size = S
     block_size = kc.size(2);
   }
   auto o = torch::empty_like(q);
@@ -128,10 +170,14 @@ torch::Tensor paged_decode(torch::Tensor q, torch::Tensor kc, torch::Tensor vc,
                       q.options().dtype(torch::kFloat32));
     ws_ptr = ws.data_ptr<float>();
   }
-  paged_decode_bf16(q.data_ptr(), kc.data_ptr(), vc.data_ptr(), bt_ptr,
-                    seq_lens.data_ptr<int>(), o.data_ptr(), ws_ptr, B, Hq,
-                    Hkv, D, (int)block_size, max_blocks, splits, (float)scale,
-                    kv_fp8 ? 1 : 0, cur_stream());
+  int rc = paged_decode_bf16(q.data_ptr(), kc.data_ptr(), vc.data_ptr(),
+                             bt_ptr, seq_lens.data_ptr<int>(), o.data_ptr(),
+                             ws_ptr, B, Hq, Hkv, D, (int)block_size,
+                             max_blocks, splits, (float)scale, kv_fp8 ? 1 : 0,
+                             cur_stream());
+  TORCH_CHECK(rc == 0, "paged_decode: configuration not supported by the "
+              "kernel (head_dim must be 64 or 128, Hq a multiple of Hkv and "
+              "Hq/Hkv in 1..8; got D=", D, " Hq=", Hq, " Hkv=", Hkv, ")");
   return o;
 }
 
@@ -141,21 +187,10 @@ torch::Tensor paged_decode(torch::Tensor q, torch::Tensor kc, torch::Tensor vc,
 // copy around the kernel.
 torch::Tensor attention_bshd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                              bool causal, double scale) {
-  TORCH_CHECK(q.is_cuda() && q.scalar_type() == torch::kBFloat16);
-  TORCH_CHECK(q.stride(3) == 1 && k.stride(3) == 1 && v.stride(3) == 1,
-              "head_dim must be contiguous");
-  int B = q.size(0), Hq = q.size(1), Sq = q.size(2), D = q.size(3);
-  int Hkv = k.size(1), Sk = k.size(2);
-  auto o = torch::empty({B, Sq, Hq, D}, q.options());
-  long long st[12] = {
-      q.stride(0), q.stride(1), q.stride(2),
-      k.stride(0), k.stride(1), k.stride(2),
-      v.stride(0), v.stride(1), v.stride(2),
-      (long long)Sq * Hq * D, D, (long long)Hq * D,
-  };
-  fa_fwd_strided_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
-                      B, Hq, Hkv, Sq, Sk, D, (float)scale, causal ? 1 : 0, st,
-                      cur_stream());
+  check_bhsd(q, "q");
+  auto o = torch::empty({q.size(0), q.size(2), q.size(1), q.size(3)},
+                        q.options());
+  attention_fwd(q, k, v, o.transpose(1, 2), causal, scale);
   return o;
 }
 
@@ -466,9 +501,6 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv3x3", &conv3x3, "NCHW implicit-GEMM 3x3 conv, fused bias+res (K3)");
   m.def("conv3x3_gn", &conv3x3_gn, "GroupNorm+SiLU fused into the K3 conv");
   m.def("softmax_fwd", &softmax_fwd);
-  m.def("tr16_probe", [](torch::Tensor out) {
-    tr16_probe((short*)out.data_ptr(), cur_stream());
-  }, "debug: ds_read_b64_tr_b16 lane/element semantics probe");
   m.def("scale_in_dev", &scale_in_dev, "x * 1/sqrt(sigma^2+1), device sigma");
   m.def("cfg_euler_dev", &cfg_euler_dev, "graph-capturable CFG+Euler step");
   m.def("step_advance", &step_advance, "increment device step counter");

@@ -37,20 +37,7 @@ DEV_INLINE short f2bf(float f) {
   return (short)((c.i + rounding_bias) >> 16);
 }
 
-// Wave-group reductions: reduce over the 16 lanes of an MFMA column group
-// (xor strides 1,2,4,8 stay inside a 16-lane group).
-DEV_INLINE float group16_max(float v) {
-#pragma unroll
-  for (int s = 1; s < 16; s <<= 1) v = fmaxf(v, __shfl_xor(v, s, WAVE));
-  return v;
-}
-
-DEV_INLINE float group16_sum(float v) {
-#pragma unroll
-  for (int s = 1; s < 16; s <<= 1) v += __shfl_xor(v, s, WAVE);
-  return v;
-}
-
+// Full-wavefront reductions (xor butterfly over all 64 lanes).
 DEV_INLINE float wave_max(float v) {
 #pragma unroll
   for (int s = 1; s < 64; s <<= 1) v = fmaxf(v, __shfl_xor(v, s, WAVE));

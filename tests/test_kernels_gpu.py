@@ -80,6 +80,72 @@ def test_attention_ragged_seq():
     _close(F.attention(q, k, v, causal=True), ref.attention_ref(q, k, v, causal=True))
 
 
+def _bf16(*shape):
+    return torch.randn(*shape, device="cuda", dtype=torch.bfloat16)
+
+
+# (name, Hq, Hkv, Sq, Sk) — q blocks are 128 rows; kv blocks are 64 rows at
+# D=64 and 32 at D=128.
+#   self:  Sq=160 is a full q block + a ragged one; Sk=160 is 2.5 kv blocks
+#          at D=64 (ragged tail) and exactly 5 at D=128 (exact edge)
+#   cross: Sk=77 is no multiple of 32 (SDXL text tokens); non-causal only
+#   gqa:   two q heads per kv head, and causal_off = Sk - Sq > 0 when causal
+_QKV_CASES = [
+    ("self", 3, 3, 160, 160),
+    ("cross", 3, 3, 160, 77),
+    ("gqa", 4, 2, 96, 224),
+]
+
+
+@requires_gpu
+@pytest.mark.parametrize("D", [64, 128])
+@pytest.mark.parametrize("case,causal", [
+    (c, causal) for c in _QKV_CASES for causal in (False, True)
+    if not (c[0] == "cross" and causal)
+], ids=lambda p: p[0] if isinstance(p, tuple) else f"causal{int(p)}")
+def test_attention_qkv_strided(case, causal, D):
+    """The stride-aware BSHD entry every model uses, fed real strided views:
+    slices of fused projections, never .contiguous() copies."""
+    name, Hq, Hkv, Sq, Sk = case
+    B = 2
+    torch.manual_seed(0)
+    if name == "self":
+        qkv = _bf16(B, Sq, 3, Hq, D)  # fused QKV projection
+        q, k, v = qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2]
+    else:
+        q = _bf16(B, Sq, Hq, D) if name == "cross" else _bf16(B, Sq, 2, Hq, D)[:, :, 1]
+        kv = _bf16(B, Sk, 2, Hkv, D)  # fused KV projection
+        k, v = kv[:, :, 0], kv[:, :, 1]
+    assert not k.is_contiguous() and not v.is_contiguous()
+    out = F.attention_qkv(q, k, v, causal=causal)
+    assert out.shape == (B, Sq, Hq * D)
+    exp = ref.attention_ref(q.transpose(1, 2), k.transpose(1, 2),
+                            v.transpose(1, 2), causal=causal)
+    _close(out, exp.transpose(1, 2).reshape(B, Sq, Hq * D))
+
+
+@requires_gpu
+def test_unsupported_attention_config_raises():
+    """An unsupported head dim or GQA group raises from the binding, on the
+    host and before any launch — it must not take the process down."""
+    lens = torch.tensor([16], device="cuda", dtype=torch.int32)
+    with pytest.raises(RuntimeError, match="supported: 64, 128"):
+        F.attention(_bf16(1, 2, 16, 80), _bf16(1, 2, 16, 80), _bf16(1, 2, 16, 80))
+    with pytest.raises(RuntimeError, match="supported: 64, 128"):
+        F.attention_qkv(_bf16(1, 16, 2, 80), _bf16(1, 16, 2, 80),
+                        _bf16(1, 16, 2, 80))
+    with pytest.raises(RuntimeError, match="supported: 64, 128"):
+        F.paged_decode(_bf16(1, 4, 80), _bf16(1, 2, 16, 80), _bf16(1, 2, 16, 80),
+                       None, lens)
+    with pytest.raises(RuntimeError, match=r"supported: 1\.\.8"):
+        F.paged_decode(_bf16(1, 32, 64), _bf16(1, 2, 16, 64), _bf16(1, 2, 16, 64),
+                       None, lens)
+    # the process and the stream are intact: a valid call still computes
+    torch.manual_seed(18)
+    q, k, v = _bf16(1, 2, 64, 64), _bf16(1, 2, 64, 64), _bf16(1, 2, 64, 64)
+    _close(F.attention(q, k, v), ref.attention_ref(q, k, v))
+
+
 @requires_gpu
 @pytest.mark.parametrize("D", [64, 128])
 def test_paged_decode_contiguous(D):
