@@ -6,7 +6,8 @@
 // Gumbel-max trick: argmax(logits/T + G_i), G_i = -log(-log(u_i)) samples the
 // softmax(logits/T) distribution in ONE read of the logits row — no max pass,
 // no sum pass, no CDF scan over a 128k vocab.  u_i comes from a counter-based
-// hash (philox-lite) of (seed, row, i) → deterministic per seed. T=0 → argmax.
+// hash (philox-lite) of (seed, row, i) → deterministic per seed. T=0 → argmax:
+// "greedy" is its own flag — every seed value, 0 included, samples at T > 0.
 #include "common.h"
 
 #define SMP_BLOCK 256
@@ -25,7 +26,8 @@ DEV_INLINE unsigned int hash3(unsigned int a, unsigned int b, unsigned int c) {
 __global__ __launch_bounds__(SMP_BLOCK) void gumbel_sample_kernel(
     const float* __restrict__ Logits,  // [rows, V] f32 (final-layer output)
     unsigned long long* __restrict__ Keys,  // [rows] packed argmax workspace
-    int rows, int V, int splits, float inv_temp, unsigned long long seed) {
+    int rows, int V, int splits, float inv_temp, unsigned long long seed,
+    int greedy) {
   int row = blockIdx.x / splits;
   int split = blockIdx.x % splits;
   if (row >= rows) return;
@@ -36,7 +38,7 @@ __global__ __launch_bounds__(SMP_BLOCK) void gumbel_sample_kernel(
   int best_i = lo;
   for (int i = lo + threadIdx.x; i < hi; i += SMP_BLOCK) {
     float s = lg[i] * inv_temp;
-    if (inv_temp != 0.f && seed != 0ull) {
+    if (!greedy) {
       unsigned int u = hash3((unsigned int)seed, (unsigned int)(seed >> 32) ^ row, i);
       float uf = (u >> 8) * (1.f / 16777216.f) + 1e-10f;
       s += -__logf(-__logf(uf));
@@ -69,8 +71,11 @@ __global__ __launch_bounds__(SMP_BLOCK) void gumbel_sample_kernel(
         best = sv[j];
         best_i = si[j];
       }
-    // pack (orderable float, ~idx) so atomicMax picks max value, min index
+    // pack (orderable float, ~idx) so atomicMax picks max value, min index.
+    // -0.0 == +0.0 in the compares above, so it must not order below +0.0
+    // here either: two splits whose maxima are zeros of unlike sign tie.
     unsigned int ub = __float_as_uint(best);
+    if ((ub << 1) == 0u) ub = 0u;
     ub = (ub & 0x80000000u) ? ~ub : (ub | 0x80000000u);
     unsigned long long key =
         ((unsigned long long)ub << 32) | (unsigned int)(~best_i);
@@ -87,14 +92,14 @@ __global__ void gumbel_unpack_kernel(const unsigned long long* __restrict__ Keys
 extern "C" void gumbel_sample(const float* logits, unsigned long long* keys,
                               int* out, int rows, int V, float temperature,
                               unsigned long long seed, hipStream_t stream) {
-  float inv_t = temperature > 0.f ? 1.f / temperature : 0.f;
-  if (temperature <= 0.f) seed = 0ull;  // greedy
+  const int greedy = temperature > 0.f ? 0 : 1;
+  float inv_t = greedy ? 1.f : 1.f / temperature;
   // fill the chip: aim for >=512 blocks (256 CUs), split each row's vocab
   int splits = 1;
   while (rows * splits < 512 && splits * SMP_BLOCK * 4 < V) splits *= 2;
   hipLaunchKernelGGL(gumbel_sample_kernel, dim3(rows * splits),
                      dim3(SMP_BLOCK), 0, stream, logits, keys, rows, V, splits,
-                     inv_t == 0.f ? 1.f : inv_t, seed);
+                     inv_t, seed, greedy);
   hipLaunchKernelGGL(gumbel_unpack_kernel, dim3((rows + 255) / 256), dim3(256),
                      0, stream, keys, out, rows);
 }
