@@ -37,6 +37,11 @@ class Request:
     prompt: List[int]
     max_new_tokens: int = 64
     temperature: float = 0.0
+    # per-request sampling controls; all four unset = the engine-wide sampler
+    top_k: int = 0                 # 0 = off
+    top_p: Optional[float] = None  # None = the engine-wide top_p
+    min_p: float = 0.0             # 0 = off
+    seed: Optional[int] = None     # None = the engine's per-step seed
     out_tokens: List[int] = field(default_factory=list)
     blocks: List[int] = field(default_factory=list)
     pos: int = 0  # tokens stored in cache
@@ -52,6 +57,14 @@ class Request:
     t_arrive: float = field(default_factory=time.monotonic)
     t_first_token: Optional[float] = None
     stream_cb: Optional[object] = None
+
+    @property
+    def custom_sampling(self) -> bool:
+        """True when the request sets any per-request sampling field; such a
+        request routes the sampling calls it takes part in to the batched
+        per-row sampler."""
+        return (self.top_k > 0 or self.top_p is not None or self.min_p > 0
+                or self.seed is not None)
 
 
 class LlamaEngine:
@@ -175,6 +188,18 @@ class LlamaEngine:
         self.lens_d = torch.ones(max_batch, dtype=torch.int32, device=dev)
         self.active_d = torch.zeros(max_batch, dtype=torch.int32, device=dev)
         self.temps_d = torch.zeros(max_batch, dtype=torch.float32, device=dev)
+        # per-slot sampling parameters of requests that set any (written when
+        # the slot is armed, reset when it is released): top_p 0 = "the
+        # engine-wide top_p", seeded 0 = "the engine's per-step seed, counter
+        # = row".  ctr_d counts a seeded request's emitted tokens on device.
+        self.topk_d = torch.zeros(max_batch, dtype=torch.int32, device=dev)
+        self.topp_d = torch.zeros(max_batch, dtype=torch.float32, device=dev)
+        self.minp_d = torch.zeros(max_batch, dtype=torch.float32, device=dev)
+        self.seeded_d = torch.zeros(max_batch, dtype=torch.bool, device=dev)
+        self.seed_d = torch.zeros(max_batch, dtype=torch.int64, device=dev)
+        self.ctr_d = torch.zeros(max_batch, dtype=torch.int64, device=dev)
+        self.rows_d = torch.arange(max_batch, dtype=torch.int64, device=dev)
+        self.batched_sample_calls = 0  # sampling calls that took that path
         self.logits_d = None
 
     # ------------------------------------------------ cold boot
@@ -230,7 +255,22 @@ class LlamaEngine:
                     presence_penalty: float = 0.0,
                     frequency_penalty: float = 0.0,
                     stop_seqs: Optional[List[List[int]]] = None,
-                    logprobs: bool = False) -> int:
+                    logprobs: bool = False, top_k: int = 0,
+                    top_p: Optional[float] = None, min_p: float = 0.0,
+                    seed: Optional[int] = None) -> int:
+        """top_k / top_p / min_p / seed are per-request sampling controls
+        (docs/ENGINE.md): top_k 0 and min_p 0 are off, top_p None takes the
+        engine-wide value, seed None the engine's per-step seed.  Out-of-
+        range values raise ValueError."""
+        if isinstance(top_k, bool) or not isinstance(top_k, int) or top_k < 0:
+            raise ValueError(f"top_k must be an integer >= 0, got {top_k!r}")
+        if top_p is not None and not 0.0 < float(top_p) <= 1.0:
+            raise ValueError(f"top_p must be in (0, 1], got {top_p!r}")
+        if not 0.0 <= float(min_p) <= 1.0:
+            raise ValueError(f"min_p must be in [0, 1], got {min_p!r}")
+        if seed is not None and (isinstance(seed, bool)
+                                 or not isinstance(seed, int)):
+            raise ValueError(f"seed must be an integer, got {seed!r}")
         limit = self.cfg.max_seq
         if len(prompt) >= limit:
             prompt = prompt[-(limit - 1):]  # keep the most recent context
@@ -241,7 +281,9 @@ class LlamaEngine:
                     stream_cb=stream_cb, presence_penalty=presence_penalty,
                     frequency_penalty=frequency_penalty,
                     stop_seqs=[list(q) for q in stop_seqs or [] if q],
-                    want_logprobs=logprobs)
+                    want_logprobs=logprobs, top_k=top_k,
+                    top_p=None if top_p is None else float(top_p),
+                    min_p=float(min_p), seed=seed)
         self._next_id += 1
         self.waiting.append(r)
         return r.req_id
@@ -318,6 +360,11 @@ class LlamaEngine:
             self.lens_d[i] = 1
             self.active_d[i] = 0
             self.bt_d[i].zero_()
+            if r.custom_sampling:
+                self.topk_d[i] = 0
+                self.topp_d[i] = 0.0
+                self.minp_d[i] = 0.0
+                self.seeded_d[i] = False
             r.slot = -1
 
     # ------------------------------------------------ prefill
@@ -356,7 +403,7 @@ class LlamaEngine:
         last_pos = torch.tensor([x - 1 for x in lens], device=self.device)
         logits = self.model.prefill(toks, kv_writer, last_pos=last_pos)
         temps = torch.tensor([r.temperature for r in group])
-        first_d = self._sample_rows(logits, temps, self.top_p)
+        first_d = self._sample_requests(logits, temps, group)
         lps = (self._logprobs_of(logits, first_d)
                if any(r.want_logprobs for r in group) else None)
         first = first_d.cpu()
@@ -374,6 +421,7 @@ class LlamaEngine:
             self.bt_d[slot, : len(r.blocks)] = bt
             self.active_d[slot] = 1
             self.temps_d[slot] = r.temperature
+            self._arm_sampling(r)
             self._pc_register(r)
 
     @staticmethod
@@ -463,6 +511,73 @@ class LlamaEngine:
                             seed=self.seed ^ (0x5EED + self._step_count))
         return torch.where(temps <= 0, greedy, sampled.to(greedy.device))
 
+    # -- per-request sampling.  Dispatch rule: a sampling call in which no
+    # row's request sets top_k / top_p / min_p / seed runs _sample_rows above,
+    # unchanged; otherwise the WHOLE call goes through the batched per-row
+    # sampler (OF.sample_batch).  There, rows without the fields take the
+    # engine-wide top_p, the engine's per-step seed and counter = row index;
+    # a seeded request draws token n from (its seed, n, its logits) alone.
+
+    def _step_seed(self) -> int:
+        return self.seed ^ (0x5EED + self._step_count)
+
+    def _arm_sampling(self, r: Request) -> None:
+        """Write r's sampling fields into its slot (r just emitted a token
+        and starts decoding)."""
+        if not r.custom_sampling:
+            return  # the slot holds the defaults since its last release
+        i = r.slot
+        self.topk_d[i] = r.top_k
+        self.topp_d[i] = 0.0 if r.top_p is None else r.top_p
+        self.minp_d[i] = r.min_p
+        self.seeded_d[i] = r.seed is not None
+        if r.seed is not None:
+            self.seed_d[i] = OF.wrap_int64(r.seed)
+            self.ctr_d[i] = len(r.out_tokens)
+
+    def _sample_requests(self, logits: torch.Tensor, temps: torch.Tensor,
+                         reqs) -> torch.Tensor:
+        """Sample one token per logits row; reqs[i] is the Request behind
+        row i.  Host-built parameters: the prefill and speculative call
+        sites assemble their rows on the host anyway."""
+        if not any(r.custom_sampling for r in reqs):
+            return self._sample_rows(logits, temps, self.top_p)
+        self._step_count += 1
+        step_seed, dev = self._step_seed(), logits.device
+        return self._sample_rows_batched(
+            logits, temps.to(dev),
+            torch.tensor([r.top_k for r in reqs], dtype=torch.int32).to(dev),
+            torch.tensor([self.top_p if r.top_p is None else r.top_p
+                          for r in reqs], dtype=torch.float32).to(dev),
+            torch.tensor([r.min_p for r in reqs],
+                         dtype=torch.float32).to(dev),
+            torch.tensor([OF.wrap_int64(step_seed if r.seed is None else r.seed)
+                          for r in reqs], dtype=torch.int64).to(dev),
+            torch.tensor([i if r.seed is None else len(r.out_tokens)
+                          for i, r in enumerate(reqs)],
+                         dtype=torch.int64).to(dev))
+
+    def _sample_slots(self, logits: torch.Tensor, lim: int) -> torch.Tensor:
+        """The decode step's batched sampling: every parameter comes from
+        the per-slot device arrays, nothing is staged or read back."""
+        self._step_count += 1
+        topp = self.topp_d[:lim]
+        seeded = self.seeded_d[:lim]
+        step_seed = OF.wrap_int64(self._step_seed())
+        return self._sample_rows_batched(
+            logits, self.temps_d[:lim], self.topk_d[:lim],
+            torch.where(topp > 0, topp, self.top_p), self.minp_d[:lim],
+            torch.where(seeded, self.seed_d[:lim], step_seed),
+            torch.where(seeded, self.ctr_d[:lim], self.rows_d[:lim]))
+
+    def _sample_rows_batched(self, logits, temps, top_k, top_p, min_p, seeds,
+                             counters) -> torch.Tensor:
+        """The batched per-row sampler; every argument is a [rows] tensor
+        on the logits' device."""
+        self.batched_sample_calls += 1
+        return OF.sample_batch(logits, temps, top_k=top_k, top_p=top_p,
+                               min_p=min_p, seeds=seeds, counters=counters)
+
     def _apply_penalties(self, logits: torch.Tensor, rows) -> None:
         """OpenAI presence/frequency penalties over the OUTPUT tokens so
         far (vLLM semantics); `rows` maps each logits row to its Request
@@ -546,7 +661,7 @@ class LlamaEngine:
         if end < len(feed):
             return False
         temps = torch.tensor([r.temperature])
-        first_d = self._sample_rows(logits[-1:], temps, self.top_p)
+        first_d = self._sample_requests(logits[-1:], temps, [r])
         lp = (self._logprobs_of(logits[-1:], first_d)[0]
               if r.want_logprobs else None)
         self._append_token(r, int(first_d.cpu()[0]), lp)
@@ -560,6 +675,7 @@ class LlamaEngine:
             r.blocks, device=dev, dtype=torch.int32)
         self.active_d[slot] = 1
         self.temps_d[slot] = r.temperature
+        self._arm_sampling(r)
         self._pc_register(r)
         return True
 
@@ -641,7 +757,10 @@ class LlamaEngine:
                 row_reqs[base] = r  # penalized requests have exactly 1 row
         self._apply_penalties(logits, row_reqs)
         temps = torch.tensor(rows_temp, dtype=torch.float32)
-        out_d = self._sample_rows(logits, temps, self.top_p)
+        rows_req: List[Optional[Request]] = []
+        for r, base, drafts in plan:
+            rows_req.extend([r] * (len(drafts) + 1))
+        out_d = self._sample_requests(logits, temps, rows_req)
         all_lps = (self._logprobs_of(logits, out_d)
                    if any(r.want_logprobs for r in self.running) else None)
         out = out_d.cpu()
@@ -700,12 +819,18 @@ class LlamaEngine:
                for r in row_reqs):
             logits = logits.clone() if logits is self.logits_d else logits
             self._apply_penalties(logits, row_reqs)
-        new_toks = self._sample_rows(logits, self.temps_d[:lim], self.top_p)
+        batched = any(r.custom_sampling for r in self.running)
+        if batched:
+            new_toks = self._sample_slots(logits, lim)
+        else:
+            new_toks = self._sample_rows(logits, self.temps_d[:lim], self.top_p)
         lps = (self._logprobs_of(logits, new_toks)
                if any(r.want_logprobs for r in self.running) else None)
         # advance device state without host staging
         self.toks_d[:lim].copy_(new_toks.long())
         self.pos_d.add_(self.active_d)
+        if batched:  # one more emitted token per live slot
+            self.ctr_d.add_(self.active_d)
         self.lens_d.copy_(self.pos_d + 1)
         toks_host = new_toks.cpu()  # the one D2H sync per step
         for r in list(self.running):

@@ -76,7 +76,12 @@ class LLMServer:
     def submit(self, prompt: str, max_tokens: int = 64, temperature: float = 0.0,
                stream_cb=None, presence_penalty: float = 0.0,
                frequency_penalty: float = 0.0, stop=None,
-               logprobs: bool = False) -> int:
+               logprobs: bool = False, top_p: Optional[float] = None,
+               top_k: int = 0, min_p: float = 0.0,
+               seed: Optional[int] = None) -> int:
+        """Queue one request.  top_p / top_k / min_p / seed are the engine's
+        per-request sampling controls; an out-of-range value raises
+        ValueError here, as a failed request does from wait()."""
         ids = self.tok.encode(prompt)
         seqs = [stop] if isinstance(stop, str) else list(stop or [])
         stop_ids = [self.tok.encode(q)[1:] for q in seqs]  # drop BOS
@@ -85,7 +90,8 @@ class LLMServer:
                 ids, max_tokens, temperature, stream_cb=stream_cb,
                 presence_penalty=presence_penalty,
                 frequency_penalty=frequency_penalty,
-                stop_seqs=[q for q in stop_ids if q], logprobs=logprobs)
+                stop_seqs=[q for q in stop_ids if q], logprobs=logprobs,
+                top_k=top_k, top_p=top_p, min_p=min_p, seed=seed)
             self._events[rid] = threading.Event()
         self._wake.set()
         return rid
@@ -117,10 +123,13 @@ class LLMServer:
     def generate(self, prompt: str, max_tokens: int = 64,
                  temperature: float = 0.0, stop=None,
                  presence_penalty: float = 0.0,
-                 frequency_penalty: float = 0.0) -> str:
+                 frequency_penalty: float = 0.0,
+                 top_p: Optional[float] = None, top_k: int = 0,
+                 min_p: float = 0.0, seed: Optional[int] = None) -> str:
         rid = self.submit(prompt, max_tokens, temperature,
                           presence_penalty=presence_penalty,
-                          frequency_penalty=frequency_penalty, stop=stop)
+                          frequency_penalty=frequency_penalty, stop=stop,
+                          top_p=top_p, top_k=top_k, min_p=min_p, seed=seed)
         r = self.wait(rid)
         toks = list(r.out_tokens)
         # engine-side early stop leaves the matched stop tokens at the
@@ -143,6 +152,26 @@ class LLMServer:
         close = getattr(self.engine, "close", None)
         if close is not None:
             close()
+
+
+def sampling_fields(body: dict, choice: int = 0) -> dict:
+    """The per-request sampling controls of an OpenAI request body as
+    submit()/generate() keywords.  Absent or null fields stay unset; with
+    `n` > 1, choice j of a seeded request uses seed + j."""
+    out: dict = {}
+    if body.get("top_p") is not None:
+        out["top_p"] = float(body["top_p"])
+    if body.get("top_k") is not None:
+        k = body["top_k"]
+        if isinstance(k, bool) or (not isinstance(k, int)
+                                   and float(k) != int(k)):
+            raise ValueError(f"top_k must be an integer >= 0, got {k!r}")
+        out["top_k"] = int(k)
+    if body.get("min_p") is not None:
+        out["min_p"] = float(body["min_p"])
+    if body.get("seed") is not None:
+        out["seed"] = int(body["seed"]) + choice
+    return out
 
 
 def create_openai_app(server: LLMServer):
@@ -204,7 +233,8 @@ def create_openai_app(server: LLMServer):
     async def _run(prompt: str, max_tokens: int, temperature: float,
                    stream: bool, chat: bool, stop=None,
                    presence_penalty: float = 0.0,
-                   frequency_penalty: float = 0.0):
+                   frequency_penalty: float = 0.0, sampling=None):
+        sampling = sampling or {}
         created = int(time.time())
         rid_str = f"cmpl-{uuid.uuid4().hex[:12]}"
         if not stream:
@@ -213,7 +243,7 @@ def create_openai_app(server: LLMServer):
                 None, lambda: server.generate(
                     prompt, max_tokens, temperature, stop=stop,
                     presence_penalty=presence_penalty,
-                    frequency_penalty=frequency_penalty))
+                    frequency_penalty=frequency_penalty, **sampling))
             usage = {"prompt_tokens": len(server.tok.encode(prompt)),
                      "completion_tokens": len(text.split()),
                      "total_tokens": len(server.tok.encode(prompt)) + len(text.split())}
@@ -239,7 +269,7 @@ def create_openai_app(server: LLMServer):
             loop.call_soon_threadsafe(q.put_nowait, tok_id)
 
         rid = server.submit(prompt, max_tokens, temperature, stream_cb=cb,
-                            stop=stop)  # engine-side early stop
+                            stop=stop, **sampling)  # engine-side early stop
 
         async def gen():
             sent = 0
@@ -298,8 +328,9 @@ def create_openai_app(server: LLMServer):
             def run_n():
                 rids = [server.submit(body.get("prompt", ""),
                                       int(body.get("max_tokens", 64)),
-                                      float(body.get("temperature", 1.0)))
-                        for _ in range(n)]
+                                      float(body.get("temperature", 1.0)),
+                                      **sampling_fields(body, j))
+                        for j in range(n)]
                 return [server.wait(rid) for rid in rids]
 
             rs = await loop.run_in_executor(None, run_n)
@@ -318,7 +349,7 @@ def create_openai_app(server: LLMServer):
                 rid = server.submit(body.get("prompt", ""),
                                     int(body.get("max_tokens", 64)),
                                     float(body.get("temperature", 0.0)),
-                                    logprobs=True)
+                                    logprobs=True, **sampling_fields(body))
                 return server.wait(rid)
 
             r = await loop.run_in_executor(None, run_lp)
@@ -339,7 +370,8 @@ def create_openai_app(server: LLMServer):
                           presence_penalty=float(
                               body.get("presence_penalty", 0) or 0),
                           frequency_penalty=float(
-                              body.get("frequency_penalty", 0) or 0))
+                              body.get("frequency_penalty", 0) or 0),
+                          sampling=sampling_fields(body))
 
     @app.post("/v1/chat/completions")
     async def chat_completions(body: dict):
@@ -352,7 +384,8 @@ def create_openai_app(server: LLMServer):
                           presence_penalty=float(
                               body.get("presence_penalty", 0) or 0),
                           frequency_penalty=float(
-                              body.get("frequency_penalty", 0) or 0))
+                              body.get("frequency_penalty", 0) or 0),
+                          sampling=sampling_fields(body))
 
     return app
 

@@ -42,6 +42,11 @@ void adamw_step(void*, const void*, float*, float*, long long, float, float,
                 float, float, float, int, int, hipStream_t);
 void gumbel_sample(const float*, unsigned long long*, int*, int, int,
                    float, unsigned long long, hipStream_t);
+void sampling_cutoff(const float*, const float*, const int*, const float*,
+                     const float*, float*, int, int, hipStream_t);
+void gumbel_sample_batch(const float*, const float*, const long long*,
+                         const long long*, const float*, unsigned long long*,
+                         int*, int, int, hipStream_t);
 void softmax_rows(const float*, float*, int, int, hipStream_t);
 void scale_in_dev_bf16(const void*, void*, const float*, const long long*,
                        long long, hipStream_t);
@@ -390,6 +395,68 @@ torch::Tensor sample_gumbel(torch::Tensor logits, double temperature,
   return out;
 }
 
+// ---- per-row filtered sampling: every parameter is a [rows] device tensor
+
+void check_logits2d(const torch::Tensor& logits) {
+  TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == torch::kFloat32,
+              "logits must be f32 GPU");
+  TORCH_CHECK(logits.dim() == 2 && logits.is_contiguous(),
+              "logits must be [rows, V] contiguous");
+  TORCH_CHECK(logits.size(0) > 0 && logits.size(1) > 0 &&
+              logits.size(1) < (1ll << 31) && logits.size(0) < (1ll << 22),
+              "logits: unsupported shape ", logits.sizes());
+}
+
+void check_row_param(const torch::Tensor& t, const torch::Tensor& logits,
+                     torch::ScalarType dt, const char* name) {
+  TORCH_CHECK(t.is_cuda() && t.device() == logits.device(), name,
+              " must be on the logits' GPU");
+  TORCH_CHECK(t.scalar_type() == dt, name, " must be ", dt);
+  TORCH_CHECK(t.dim() == 1 && t.size(0) == logits.size(0), name,
+              " must have one value per row ([", logits.size(0), "]), got ",
+              t.sizes());
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+}
+
+torch::Tensor sampling_cutoff_fwd(torch::Tensor logits, torch::Tensor temps,
+                                  torch::Tensor top_k, torch::Tensor top_p,
+                                  torch::Tensor min_p) {
+  check_logits2d(logits);
+  check_row_param(temps, logits, torch::kFloat32, "temperature");
+  check_row_param(top_k, logits, torch::kInt32, "top_k");
+  check_row_param(top_p, logits, torch::kFloat32, "top_p");
+  check_row_param(min_p, logits, torch::kFloat32, "min_p");
+  int rows = logits.size(0), V = logits.size(1);
+  auto cut = torch::empty({rows}, logits.options());
+  sampling_cutoff(logits.data_ptr<float>(), temps.data_ptr<float>(),
+                  top_k.data_ptr<int>(), top_p.data_ptr<float>(),
+                  min_p.data_ptr<float>(), cut.data_ptr<float>(), rows, V,
+                  cur_stream());
+  return cut;
+}
+
+torch::Tensor sample_batch(torch::Tensor logits, torch::Tensor temps,
+                           torch::Tensor seeds, torch::Tensor counters,
+                           c10::optional<torch::Tensor> cutoff) {
+  check_logits2d(logits);
+  check_row_param(temps, logits, torch::kFloat32, "temperature");
+  check_row_param(seeds, logits, torch::kInt64, "seeds");
+  check_row_param(counters, logits, torch::kInt64, "counters");
+  if (cutoff.has_value())
+    check_row_param(*cutoff, logits, torch::kFloat32, "cutoff");
+  int rows = logits.size(0), V = logits.size(1);
+  auto out = torch::empty({rows}, logits.options().dtype(torch::kInt32));
+  auto keys = torch::zeros({rows}, logits.options().dtype(torch::kInt64));
+  gumbel_sample_batch(
+      logits.data_ptr<float>(), temps.data_ptr<float>(),
+      (const long long*)seeds.data_ptr<int64_t>(),
+      (const long long*)counters.data_ptr<int64_t>(),
+      cutoff.has_value() ? cutoff->data_ptr<float>() : nullptr,
+      (unsigned long long*)keys.data_ptr<int64_t>(), out.data_ptr<int>(),
+      rows, V, cur_stream());
+  return out;
+}
+
 torch::Tensor softmax_fwd(torch::Tensor x) {
   TORCH_CHECK(x.is_cuda() && x.scalar_type() == torch::kFloat32);
   int V = x.size(-1);
@@ -498,6 +565,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("rope_", &rope_, "in-place RoPE with host cos/sin tables");
   m.def("adamw_", &adamw_, "fused AdamW step (K9)");
   m.def("sample_gumbel", &sample_gumbel, "fused sampling (K8)");
+  m.def("sample_batch", &sample_batch,
+        "per-row temperature/seed/counter/cutoff gumbel sampling (K8)");
+  m.def("sampling_cutoff", &sampling_cutoff_fwd,
+        "per-row top-k/top-p/min-p logit cutoff by radix select (K8)");
   m.def("conv3x3", &conv3x3, "NCHW implicit-GEMM 3x3 conv, fused bias+res (K3)");
   m.def("conv3x3_gn", &conv3x3_gn, "GroupNorm+SiLU fused into the K3 conv");
   m.def("softmax_fwd", &softmax_fwd);

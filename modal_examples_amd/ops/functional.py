@@ -280,6 +280,93 @@ def sample(logits, temperature: float = 1.0, seed: int = 0):
     return ext.sample_gumbel(logits.float().contiguous(), temperature, seed)
 
 
+def wrap_int64(v: int) -> int:
+    """Any Python int as the int64 with the same low 64 bits (seeds are
+    64-bit patterns; an int64 tensor carries them to the kernel)."""
+    v = int(v) & (1 << 64) - 1
+    return v - (1 << 64) if v >= 1 << 63 else v
+
+
+def _row_param(v, rows: int, dtype, device, name: str) -> torch.Tensor:
+    """A per-row sampling parameter as a contiguous [rows] tensor on `device`:
+    a Python scalar is broadcast by a device fill, a tensor must already have
+    one value per row.  Nothing here reads a value back to the host."""
+    if isinstance(v, torch.Tensor):
+        if v.dim() == 0:
+            v = v.expand(rows)
+        if v.dim() != 1 or v.shape[0] != rows:
+            raise ValueError(f"{name} must have one value per row ([{rows}]), "
+                             f"got {tuple(v.shape)}")
+        if v.device != device:
+            raise ValueError(f"{name} is on {v.device}, logits on {device}")
+        return v.to(dtype).contiguous()
+    if dtype is torch.int64:
+        v = wrap_int64(v)
+    return torch.full((rows,), v, dtype=dtype, device=device)
+
+
+def _check_logits_2d(logits):
+    if logits.dim() != 2 or logits.shape[0] == 0 or logits.shape[1] == 0:
+        raise ValueError(f"logits must be [rows, V], got {tuple(logits.shape)}")
+
+
+def _filter_params(logits, temperature, top_k, top_p, min_p):
+    rows, dev = logits.shape[0], logits.device
+    return (_row_param(temperature, rows, torch.float32, dev, "temperature"),
+            _row_param(0 if top_k is None else top_k, rows, torch.int32, dev,
+                       "top_k"),
+            _row_param(1.0 if top_p is None else top_p, rows, torch.float32,
+                       dev, "top_p"),
+            _row_param(0.0 if min_p is None else min_p, rows, torch.float32,
+                       dev, "min_p"))
+
+
+def sampling_cutoff(logits, temperature, top_k=None, top_p=None, min_p=None):
+    """Per-row cutoff logit c_r of the top-k / top-p / min-p filters (K8):
+    the filtered distribution of row r lives on {i : logits[r, i] >= c_r}.
+
+    logits [B, V]; every parameter is a [B] tensor or a Python scalar that
+    is broadcast; None is off (so are top_k 0 or >= V, top_p 1, min_p 0).
+    top-p is applied to the survivors of top-k and renormalised over them;
+    ties at a threshold are all kept.  Rows with every filter off, or with
+    temperature <= 0, get -inf.  Returns float32 [B]."""
+    _check_logits_2d(logits)
+    t, k, p, q = _filter_params(logits, temperature, top_k, top_p, min_p)
+    ext = _ext_for(logits, any_dtype=True)
+    if ext is None:
+        return ref.sampling_cutoff_ref(logits, t, k, p, q)
+    return ext.sampling_cutoff(logits.float().contiguous(), t, k, p, q)
+
+
+def sample_batch(logits, temperature, top_k=None, top_p=None, min_p=None,
+                 seeds=None, counters=None):
+    """Batched sampling with per-row parameters (K8): gumbel-max over the
+    filtered softmax(logits/T), T <= 0 -> first arg-max.
+
+    Each parameter is a [B] tensor or a Python scalar that is broadcast;
+    None is off, seeds default to 0 and counters to the row index.  The draw
+    of a row depends on its (seed, counter, logits) only — not on its index
+    or on the rest of the batch.  `sample(x, T, seed=s)` is the special case
+    `sample_batch(x, T, seeds=s, counters=arange(B))`.  Returns int32 [B]."""
+    _check_logits_2d(logits)
+    rows, dev = logits.shape[0], logits.device
+    s = _row_param(0 if seeds is None else seeds, rows, torch.int64, dev,
+                   "seeds")
+    c = (torch.arange(rows, dtype=torch.int64, device=dev) if counters is None
+         else _row_param(counters, rows, torch.int64, dev, "counters"))
+    ext = _ext_for(logits, any_dtype=True)
+    if ext is None:
+        t, k, p, q = _filter_params(logits, temperature, top_k, top_p, min_p)
+        return ref.sample_batch_ref(logits, t, k, p, q, s, c)
+    lg = logits.float().contiguous()
+    if top_k is None and top_p is None and min_p is None:
+        # unfiltered calls launch no cutoff kernel at all
+        t = _row_param(temperature, rows, torch.float32, dev, "temperature")
+        return ext.sample_batch(lg, t, s, c, None)
+    t, k, p, q = _filter_params(logits, temperature, top_k, top_p, min_p)
+    return ext.sample_batch(lg, t, s, c, ext.sampling_cutoff(lg, t, k, p, q))
+
+
 def softmax(x):
     ext = _ext_for(x, any_dtype=True)
     if ext is None:

@@ -120,3 +120,97 @@ def adamw_ref(p, g, m, v, lr, beta1, beta2, eps, wd, step):
     pf = pf - lr * (mhat / (vhat.sqrt() + eps) + wd * pf)
     p.copy_(pf.to(p.dtype))
     return p
+
+
+# ------------------------------------------------ per-row filtered sampling
+# float64 models of sampling_cutoff / sample_batch (csrc/sampling.hip).  The
+# kept set of a row is {i : logit_i >= cutoff}; ties at a threshold are all
+# kept.  The uniform draws use the kernel's own integer hash, so a CPU engine
+# is deterministic and agrees with the GPU except at near-ties.
+
+_M32 = 0xFFFFFFFF
+
+
+def _hash3(a, b, c):
+    """The kernel's hash3 on uint32 values held in int64 tensors (products
+    wrap mod 2^64, which leaves their low 32 bits exact)."""
+    h = (a * 0x9E3779B1 ^ b * 0x85EBCA77 ^ c * 0xC2B2AE3D) & _M32
+    h = h ^ (h >> 15)
+    h = (h * 0x2C1B3C6D) & _M32
+    h = h ^ (h >> 12)
+    h = (h * 0x297A2D39) & _M32
+    return h ^ (h >> 15)
+
+
+def sampling_cutoff_ref(logits, temperature, top_k, top_p, min_p):
+    """Cutoff logit per row, float32 [B].  Parameters are [B] tensors:
+    temperature/top_p/min_p float32, top_k integer.  top_k 0 or >= V, top_p
+    >= 1 and min_p <= 0 are off; a row with every filter off, or with
+    temperature <= 0, gets -inf.  A -inf logit is never kept by a filter."""
+    x = logits.detach().double()
+    B, V = x.shape
+    ninf = float("-inf")
+    T = temperature.double()
+    live = T > 0
+    T = torch.where(live, T, torch.ones_like(T))
+    k = top_k.long()
+    p = top_p.double()
+    q = min_p.double()
+    xs = x.sort(-1, descending=True).values
+    finite = xs > ninf
+    nfin = finite.sum(-1)
+    k_on, p_on, q_on = (k > 0) & (k < V), p < 1, q > 0
+    # top-k: the k-th largest finite logit (pure ordering)
+    kth = (torch.minimum(k, nfin) - 1).clamp_(min=0)
+    c_k = torch.where(k_on, xs.gather(1, kth[:, None])[:, 0],
+                      torch.full_like(T, ninf))
+    in_k = finite & (xs >= c_k[:, None])
+    # top-p over the survivors: keep i iff the mass strictly above it is
+    # <= p * Z_K; equal logits share the mass above their group
+    s = xs / T[:, None]
+    e_all = torch.exp(s - s[:, :1])
+    e_all = torch.where(finite, e_all, torch.zeros_like(e_all))
+    e = torch.where(in_k, e_all, torch.zeros_like(e_all))
+    before = e.cumsum(-1) - e
+    pos = torch.arange(V).expand(B, V)
+    start = torch.ones(B, V, dtype=torch.bool)
+    start[:, 1:] = xs[:, 1:] != xs[:, :-1]
+    gstart = torch.where(start, pos, torch.zeros_like(pos)).cummax(-1).values
+    above = before.gather(1, gstart)
+    keep_p = in_k & (above <= (p * e.sum(-1))[:, None])
+    pinf = torch.full_like(xs, float("inf"))
+    c_p = torch.where(keep_p, xs, pinf).min(-1).values
+    # min-p: p_i >= q * p_max
+    c_q = torch.where(finite & (e_all >= q[:, None]), xs, pinf).min(-1).values
+    c = c_k
+    c = torch.where(p_on, torch.maximum(c, c_p), c)
+    c = torch.where(q_on, torch.maximum(c, c_q), c)
+    c = torch.where(live & (k_on | p_on | q_on), c, torch.full_like(c, ninf))
+    return c.float()
+
+
+def gumbel_scores_ref(logits, temperature, seeds, counters):
+    """float64 scores logit * f32(1/T) + G(seed, counter, i), [B, V]; the
+    uniform behind G is formed in float32 exactly as the kernel forms it."""
+    B, V = logits.shape
+    seeds, counters = seeds.long(), counters.long()
+    lo = (seeds & _M32)[:, None]
+    hi = (((seeds >> 32) & _M32) ^ (counters & _M32))[:, None]
+    u = _hash3(lo, hi, torch.arange(V, dtype=torch.long)[None, :])
+    uf = (u >> 8).float() * (1.0 / 16777216.0) + 1e-10
+    gumbel = -torch.log(-torch.log(uf.double()))
+    inv_t = (1.0 / temperature.float()).double()
+    return logits.detach().double() * inv_t[:, None] + gumbel
+
+
+def sample_batch_ref(logits, temperature, top_k, top_p, min_p, seeds, counters):
+    """Token per row, int32 [B]: arg-max of the gumbel scores over the kept
+    set, first index on ties; temperature <= 0 is the plain arg-max."""
+    lg = logits.detach().float()
+    temperature = temperature.float()
+    live = temperature > 0
+    cut = sampling_cutoff_ref(lg, temperature, top_k, top_p, min_p)
+    safe_t = torch.where(live, temperature, torch.ones_like(temperature))
+    scores = gumbel_scores_ref(lg, safe_t, seeds, counters)
+    scores = scores.masked_fill(~(lg >= cut[:, None]), float("-inf"))
+    return torch.where(live, scores.argmax(-1), lg.argmax(-1)).int()
