@@ -53,11 +53,17 @@ struct FA32Strides {
 // DEFER: defer-max rescale skipping (HK THR=8) — keep the old running max
 // while per-block growth <= 8, so P = exp(s - m_old) <= e^8 (f32 acc safe)
 // and the O-wide rescale is skipped entirely.
+// The D=64 causal instance sits at the 3-waves/SIMD register edge (168); the
+// waves-per-SIMD request keeps it there now that m_run outlives the loop for
+// the LSE.  1 is the launch-bounds default and changes nothing elsewhere.
 template <int D, bool CAUSAL, int KVB, bool DEFER>
-__global__ __launch_bounds__(FA32_NWAVES * WAVE) void fa32_kernel(
+__global__ __launch_bounds__(FA32_NWAVES * WAVE)
+__attribute__((amdgpu_waves_per_eu((D == 64 && CAUSAL) ? 3 : 1)))
+void fa32_kernel(
     const short* __restrict__ Q, const short* __restrict__ K,
     const short* __restrict__ V, short* __restrict__ O,
-    int B, int Hq, int Hkv, int Sq, int Sk, float scale, FA32Strides st) {
+    float* __restrict__ LSE, int B, int Hq, int Hkv, int Sq, int Sk,
+    float scale, FA32Strides st) {
   constexpr int KROW = D + FA32_PPAD;
   constexpr int DCH = D / 16;  // QK^T k-chunks (K-dim 16)
   constexpr int DT = D / 32;   // PV d-tiles (M-dim 32)
@@ -266,6 +272,11 @@ __global__ __launch_bounds__(FA32_NWAVES * WAVE) void fa32_kernel(
 
   // ---- epilogue: O[q][d] = O^T[d][q] / l ----
   if (my_q < Sq) {
+    // log-sum-exp of the scaled scores for the backward: l_run is always
+    // sum exp(s - m_run), with defer-max on or off.  Both lane halves hold
+    // the same pair; the low half writes.
+    if (LSE != nullptr && hi5 == 0)
+      LSE[((long long)b * Hq + h) * Sq + my_q] = m_run + logf(l_run);
     float inv = l_run > 0.f ? 1.f / l_run : 0.f;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt)
@@ -280,10 +291,11 @@ __global__ __launch_bounds__(FA32_NWAVES * WAVE) void fa32_kernel(
 // q/k/v/o are logically [B,H,S,D] with d contiguous; strides[12] holds the
 // element strides qb qh qs kb kh ks vb vh vs ob oh os.  Returns 0 once the
 // kernel is launched, non-zero (nothing launched) for an unsupported
-// configuration: D must be 64 or 128 and Hq a multiple of Hkv.
+// configuration: D must be 64 or 128 and Hq a multiple of Hkv.  lse, when
+// not null, receives the fp32 log-sum-exp per query row, [B,Hq,Sq] contiguous.
 extern "C" int fa32_fwd_strided_bf16(
-    const void* q, const void* k, const void* v, void* o, int B, int Hq,
-    int Hkv, int Sq, int Sk, int D, float scale, int causal,
+    const void* q, const void* k, const void* v, void* o, float* lse, int B,
+    int Hq, int Hkv, int Sq, int Sk, int D, float scale, int causal,
     const long long* strides, hipStream_t stream) {
   if ((D != 64 && D != 128) || Hkv <= 0 || Hq % Hkv != 0) return 1;
   const short* Qp = (const short*)q;
@@ -307,10 +319,12 @@ extern "C" int fa32_fwd_strided_bf16(
   do {                                                                        \
     if (defer_env)                                                            \
       hipLaunchKernelGGL((fa32_kernel<DD, CC, KK, true>), grid, block, 0,     \
-                         stream, Qp, Kp, Vp, Op, B, Hq, Hkv, Sq, Sk, scale, st); \
+                         stream, Qp, Kp, Vp, Op, lse, B, Hq, Hkv, Sq, Sk,     \
+                         scale, st);                                          \
     else                                                                      \
       hipLaunchKernelGGL((fa32_kernel<DD, CC, KK, false>), grid, block, 0,    \
-                         stream, Qp, Kp, Vp, Op, B, Hq, Hkv, Sq, Sk, scale, st); \
+                         stream, Qp, Kp, Vp, Op, lse, B, Hq, Hkv, Sq, Sk,     \
+                         scale, st);                                          \
   } while (0)
   if (D == 64) {
     if (causal) L32K(64, true, 64); else L32K(64, false, 64);

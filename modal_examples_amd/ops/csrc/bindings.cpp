@@ -14,11 +14,15 @@
 
 // ---- extern "C" launchers from the .hip translation units ----
 extern "C" {
-// the two attention launchers return 0 once launched, non-zero (nothing
+// the attention launchers return 0 once launched, non-zero (nothing
 // launched) for a configuration they do not support
-int fa32_fwd_strided_bf16(const void*, const void*, const void*, void*, int,
-                          int, int, int, int, int, float, int,
+int fa32_fwd_strided_bf16(const void*, const void*, const void*, void*, float*,
+                          int, int, int, int, int, int, float, int,
                           const long long*, hipStream_t);
+int fa_bwd_strided_bf16(const void*, const void*, const void*, const void*,
+                        const void*, const float*, float*, void*, void*, void*,
+                        int, int, int, int, int, int, float, int,
+                        const long long*, hipStream_t);
 int paged_decode_bf16(const void*, const void*, const void*, const int*,
                       const int*, void*, float*, int, int, int, int, int,
                       int, int, float, int, hipStream_t);
@@ -86,9 +90,10 @@ void check_bhsd(const torch::Tensor& t, const char* name) {
 // The one forward-attention launch: q/k/v/o are logically [B,H,S,D] with ANY
 // batch/head/sequence strides (d contiguous), read straight off the tensors.
 // Unsupported configurations raise here, before anything is launched.
+// lse, when not null, receives the fp32 log-sum-exp per query row [B,Hq,Sq].
 void attention_fwd(const torch::Tensor& q, const torch::Tensor& k,
                    const torch::Tensor& v, const torch::Tensor& o, bool causal,
-                   double scale) {
+                   double scale, float* lse = nullptr) {
   check_bhsd(q, "q");
   check_bhsd(k, "k");
   check_bhsd(v, "v");
@@ -107,7 +112,7 @@ void attention_fwd(const torch::Tensor& q, const torch::Tensor& k,
       o.stride(0), o.stride(1), o.stride(2),
   };
   int rc = fa32_fwd_strided_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                                 o.data_ptr(), B, Hq, Hkv, Sq, Sk, D,
+                                 o.data_ptr(), lse, B, Hq, Hkv, Sq, Sk, D,
                                  (float)scale, causal ? 1 : 0, st,
                                  cur_stream());
   TORCH_CHECK(rc == 0, "attention: configuration not supported by the kernel "
@@ -197,6 +202,91 @@ torch::Tensor attention_bshd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                         q.options());
   attention_fwd(q, k, v, o.transpose(1, 2), causal, scale);
   return o;
+}
+
+// Training forward: the same launch, also saving the log-sum-exp that the
+// backward recomputes P from.  q/k/v may be strided (d contiguous).
+torch::Tensor new_lse(const torch::Tensor& q) {
+  check_bhsd(q, "q");
+  return torch::empty({q.size(0), q.size(1), q.size(2)},
+                      q.options().dtype(torch::kFloat32));
+}
+
+std::tuple<torch::Tensor, torch::Tensor> attention_fwd_lse(
+    torch::Tensor q, torch::Tensor k, torch::Tensor v, bool causal,
+    double scale) {
+  auto lse = new_lse(q);
+  auto o = torch::empty(q.sizes(), q.options());
+  attention_fwd(q, k, v, o, causal, scale, lse.data_ptr<float>());
+  return {o, lse};
+}
+
+// ... and its sibling with the [B,S,H,D]-contiguous output of attention_bshd
+std::tuple<torch::Tensor, torch::Tensor> attention_fwd_lse_bshd(
+    torch::Tensor q, torch::Tensor k, torch::Tensor v, bool causal,
+    double scale) {
+  auto lse = new_lse(q);
+  auto o = torch::empty({q.size(0), q.size(2), q.size(1), q.size(3)},
+                        q.options());
+  attention_fwd(q, k, v, o.transpose(1, 2), causal, scale,
+                lse.data_ptr<float>());
+  return {o, lse};
+}
+
+// Attention backward into caller-provided dq/dk/dv.  Everything is logically
+// [B,H,S,D] with any batch/head/sequence strides (d contiguous); every check
+// raises before anything is launched.
+void attention_bwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
+                   torch::Tensor o, torch::Tensor lse, torch::Tensor dout,
+                   torch::Tensor dq, torch::Tensor dk, torch::Tensor dv,
+                   bool causal, double scale) {
+  check_bhsd(q, "q");
+  check_bhsd(k, "k");
+  check_bhsd(v, "v");
+  check_bhsd(o, "o");
+  check_bhsd(dout, "dout");
+  check_bhsd(dq, "dq");
+  check_bhsd(dk, "dk");
+  check_bhsd(dv, "dv");
+  int B = q.size(0), Hq = q.size(1), Sq = q.size(2), D = q.size(3);
+  int Hkv = k.size(1), Sk = k.size(2);
+  TORCH_CHECK(D == 64 || D == 128, "attention_bwd: unsupported head_dim ", D,
+              " (supported: 64, 128)");
+  TORCH_CHECK(k.size(0) == B && k.size(3) == D && v.sizes() == k.sizes(),
+              "attention_bwd: k/v must be [B,Hkv,Sk,D] matching q's B and D");
+  TORCH_CHECK(Hkv > 0 && Hq % Hkv == 0, "GQA requires Hq % Hkv == 0, got Hq=",
+              Hq, " Hkv=", Hkv);
+  TORCH_CHECK(B >= 1 && Sq >= 1 && Sk >= 1, "attention_bwd: empty input");
+  TORCH_CHECK(o.sizes() == q.sizes() && dout.sizes() == q.sizes(),
+              "attention_bwd: o and dout must have q's shape");
+  TORCH_CHECK(dq.sizes() == q.sizes() && dk.sizes() == k.sizes() &&
+              dv.sizes() == v.sizes(),
+              "attention_bwd: dq/dk/dv must have the shapes of q/k/v");
+  TORCH_CHECK(lse.is_cuda() && lse.scalar_type() == torch::kFloat32 &&
+              lse.dim() == 3 && lse.size(0) == B && lse.size(1) == Hq &&
+              lse.size(2) == Sq && lse.is_contiguous(),
+              "attention_bwd: lse must be fp32 [B,Hq,Sq] contiguous");
+  TORCH_CHECK(!causal || Sk >= Sq, "attention_bwd: causal requires Sk >= Sq, "
+              "got Sq=", Sq, " Sk=", Sk);
+  auto delta = torch::empty_like(lse);
+  long long st[24] = {
+      q.stride(0), q.stride(1), q.stride(2),
+      k.stride(0), k.stride(1), k.stride(2),
+      v.stride(0), v.stride(1), v.stride(2),
+      o.stride(0), o.stride(1), o.stride(2),
+      dout.stride(0), dout.stride(1), dout.stride(2),
+      dq.stride(0), dq.stride(1), dq.stride(2),
+      dk.stride(0), dk.stride(1), dk.stride(2),
+      dv.stride(0), dv.stride(1), dv.stride(2),
+  };
+  int rc = fa_bwd_strided_bf16(
+      q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), dout.data_ptr(),
+      lse.data_ptr<float>(), delta.data_ptr<float>(), dq.data_ptr(),
+      dk.data_ptr(), dv.data_ptr(), B, Hq, Hkv, Sq, Sk, D, (float)scale,
+      causal ? 1 : 0, st, cur_stream());
+  TORCH_CHECK(rc == 0, "attention_bwd: configuration not supported by the "
+              "kernel (got D=", D, " Hq=", Hq, " Hkv=", Hkv, " Sq=", Sq,
+              " Sk=", Sk, " causal=", causal, ")");
 }
 
 // ---------------------------------------------------------------- norms
@@ -553,6 +643,12 @@ void snap_free(int64_t id) {
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attention", &attention, "flash attention fwd bf16 (K1/K5/K7)");
   m.def("attention_bshd", &attention_bshd, "stride-aware attention, BSHD out");
+  m.def("attention_fwd_lse", &attention_fwd_lse,
+        "attention fwd returning (o, lse) for the backward");
+  m.def("attention_fwd_lse_bshd", &attention_fwd_lse_bshd,
+        "attention fwd returning (o [B,S,H,D], lse)");
+  m.def("attention_bwd", &attention_bwd,
+        "flash attention bwd bf16 into caller-provided dq/dk/dv");
   m.def("paged_decode", &paged_decode, "paged KV decode attention (K6)");
   m.def("groupnorm_silu", &groupnorm_silu);
   m.def("layernorm", &layernorm);

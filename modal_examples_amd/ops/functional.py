@@ -9,6 +9,7 @@ testable without hardware.
 from __future__ import annotations
 
 import math
+import os
 from typing import Optional
 
 import torch
@@ -19,10 +20,11 @@ from ._build import get_ext
 
 def _ext_for(t: torch.Tensor, *grad_tensors, any_dtype: bool = False):
     """Dispatch: hand kernel on GPU for inference; differentiable torch
-    composition when autograd needs to flow (training forward) — the custom
-    kernels are forward-only, so grad-mode falls back to reference math on
-    the SAME device (hipBLASLt/eager ROCm kernels), keeping LoRA/backward
-    correct end-to-end.
+    composition when autograd needs to flow (training forward) — apart from
+    attention, which has its own HIP backward (see `_attn_train_ext`), the
+    custom kernels are forward-only, so grad-mode falls back to reference
+    math on the SAME device (hipBLASLt/eager ROCm kernels), keeping
+    LoRA/backward correct end-to-end.
 
     Most kernels are bf16-native (CDNA4 MFMA tiles); a non-bf16 GPU tensor
     (e.g. an fp32 research model) runs the reference composition on the same
@@ -37,16 +39,85 @@ def _ext_for(t: torch.Tensor, *grad_tensors, any_dtype: bool = False):
         if not any_dtype and t.dtype is not torch.bfloat16:
             get_ext(required=True)  # still verify the .so is present
             return None
-        ext = get_ext(required=True)
-        from ..gpu.guard import SyncProxy, debug_sync_enabled
-
-        return SyncProxy(ext) if debug_sync_enabled() else ext
+        return _sync_wrapped(get_ext(required=True))
     return None
 
 
+def _sync_wrapped(ext):
+    from ..gpu.guard import SyncProxy, debug_sync_enabled
+
+    return SyncProxy(ext) if debug_sync_enabled() else ext
+
+
+def _attn_train_ext(q, k, v, causal: bool):
+    """The extension, when a grad-mode attention call runs the HIP forward
+    (saving the log-sum-exp) and the HIP backward: inputs on the GPU in bf16,
+    head_dim 64 or 128, and not (causal with Sq > Sk).  None otherwise — CPU,
+    fp32, other head dims, or MODAL_AMD_ATTN_BWD=ref (read at call time; the
+    A/B switch back to the differentiable reference) keep the reference path.
+    q/k/v are [B,H,S,D]-logical."""
+    if not (torch.is_grad_enabled()
+            and any(t.requires_grad for t in (q, k, v))):
+        return None
+    if os.environ.get("MODAL_AMD_ATTN_BWD", "") == "ref":
+        return None
+    if not all(t.is_cuda and t.dtype is torch.bfloat16 for t in (q, k, v)):
+        return None
+    if q.shape[-1] not in (64, 128) or (causal and q.shape[2] > k.shape[2]):
+        return None
+    return _sync_wrapped(get_ext(required=True))
+
+
+def _d_contiguous(t):
+    return t if t.stride(-1) == 1 else t.contiguous()
+
+
+class _AttentionFn(torch.autograd.Function):
+    """Differentiable flash attention on the gfx950 kernels.  q/k/v are
+    [B,H,S,D]-logical with any strides (d contiguous); the forward saves o
+    and one fp32 log-sum-exp per query row, the backward recomputes P from
+    it (csrc/attention_bwd.hip) — O(S) extra memory, no score matrix.
+    bshd=True returns o as [B,S,H,D] contiguous (attention_qkv)."""
+
+    @staticmethod
+    def forward(ctx, q, k, v, causal, scale, bshd, ext):
+        q, k, v = _d_contiguous(q), _d_contiguous(k), _d_contiguous(v)
+        if bshd:
+            o, lse = ext.attention_fwd_lse_bshd(q, k, v, causal, scale)
+        else:
+            o, lse = ext.attention_fwd_lse(q, k, v, causal, scale)
+        ctx.save_for_backward(q, k, v, o, lse)
+        ctx.causal, ctx.scale, ctx.bshd, ctx.ext = causal, scale, bshd, ext
+        return o
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        q, k, v, o, lse = ctx.saved_tensors
+        if ctx.bshd:  # o and its gradient are [B,S,H,D]; the kernel wants BHSD
+            o, dout = o.transpose(1, 2), dout.transpose(1, 2)
+        dout = _d_contiguous(dout)
+
+        def grad_like(t):  # sequence-major for sequence-major callers
+            if ctx.bshd:
+                B, H, S, D = t.shape
+                return torch.empty(B, S, H, D, dtype=t.dtype,
+                                   device=t.device).transpose(1, 2)
+            return torch.empty(t.shape, dtype=t.dtype, device=t.device)
+
+        dq, dk, dv = grad_like(q), grad_like(k), grad_like(v)
+        ctx.ext.attention_bwd(q, k, v, o, lse, dout, dq, dk, dv, ctx.causal,
+                              ctx.scale)
+        return dq, dk, dv, None, None, None, None
+
+
 def attention(q, k, v, causal: bool = False, scale: Optional[float] = None):
-    """Flash attention fwd (K1/K5/K7). q [B,Hq,Sq,D], k/v [B,Hkv,Sk,D] bf16."""
+    """Flash attention (K1/K5/K7). q [B,Hq,Sq,D], k/v [B,Hkv,Sk,D] bf16.
+    Differentiable on the GPU through the HIP backward."""
     scale = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
+    ext = _attn_train_ext(q, k, v, causal)
+    if ext is not None:
+        return _AttentionFn.apply(q, k, v, causal, scale, False, ext)
     ext = _ext_for(q, k, v)
     if ext is None:
         return ref.attention_ref(q, k, v, causal, scale)
@@ -59,11 +130,19 @@ def attention_qkv(q, k, v, causal: bool = False, scale: Optional[float] = None):
     q: [B, S, Hq, D] (any strides, d contiguous — e.g. a slice of a fused QKV
     projection); k/v: [B, Sk, Hkv, D].  Returns [B, S, Hq*D] contiguous,
     ready for the output projection.  On GPU the kernel reads the strided
-    layouts directly and writes BSHD — no .contiguous() copies at all.
+    layouts directly and writes BSHD — no .contiguous() copies at all; in
+    grad mode the backward reads the same views and the [B,S,Hq*D] output
+    gradient in place.
     """
     B, S, Hq, D = q.shape
     Sk, Hkv = k.shape[1], k.shape[2]
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    ext = _attn_train_ext(q.transpose(1, 2), k.transpose(1, 2),
+                          v.transpose(1, 2), causal)
+    if ext is not None:
+        o = _AttentionFn.apply(q.transpose(1, 2), k.transpose(1, 2),
+                               v.transpose(1, 2), causal, scale, True, ext)
+        return o.view(B, S, Hq * D)
     ext = _ext_for(q, k, v)
     if ext is None:
         o = ref.attention_ref(q.transpose(1, 2), k.transpose(1, 2),

@@ -18,7 +18,7 @@ def attention_ref(q, k, v, causal: bool = False, scale: Optional[float] = None):
     B, Hq, Sq, D = q.shape
     Hkv, Sk = k.shape[1], k.shape[2]
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
-    qf, kf, vf = q.float(), k.float(), v.float()
+    qf, kf, vf = _wide(q), _wide(k), _wide(v)
     if Hkv != Hq:
         rep = Hq // Hkv
         kf = kf.repeat_interleave(rep, dim=1)
@@ -30,6 +30,75 @@ def attention_ref(q, k, v, causal: bool = False, scale: Optional[float] = None):
         s = s.masked_fill(~mask, float("-inf"))
     p = torch.softmax(s, dim=-1)
     return torch.matmul(p, vf).to(q.dtype)
+
+
+def _wide(t):
+    """fp32 working precision; fp64 inputs stay fp64 (truth for tests)."""
+    return t if t.dtype is torch.float64 else t.float()
+
+
+def _masked_scores(q, k, causal, scale):
+    """Scaled scores [B,Hkv,G,Sq,Sk] (GQA group as its own axis), -inf where
+    the causal mask (offset Sk - Sq) hides a key."""
+    B, Hq, Sq, D = q.shape
+    Hkv, Sk = k.shape[1], k.shape[2]
+    qg = _wide(q).reshape(B, Hkv, Hq // Hkv, Sq, D)
+    s = torch.matmul(qg, _wide(k).unsqueeze(2).transpose(-1, -2)) * scale
+    if causal:
+        mask = torch.ones(Sq, Sk, dtype=torch.bool,
+                          device=q.device).tril(Sk - Sq)
+        s = s.masked_fill(~mask, float("-inf"))
+    return s
+
+
+def attention_lse_ref(q, k, causal: bool = False,
+                      scale: Optional[float] = None):
+    """Log-sum-exp of the scaled, masked scores per query row: [B,Hq,Sq] in
+    the working precision — what the forward kernel saves for the backward."""
+    B, Hq, Sq, D = q.shape
+    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    s = _masked_scores(q, k, causal, scale)
+    return torch.logsumexp(s, dim=-1).reshape(B, Hq, Sq)
+
+
+def attention_bwd_ref(q, k, v, o, lse, dout, causal: bool = False,
+                      scale: Optional[float] = None,
+                      emulate_bf16: bool = False):
+    """Attention backward by recompute-from-LSE — the algorithm of
+    csrc/attention_bwd.hip in torch, and its specification.
+
+    q/o/dout [B,Hq,Sq,D], k/v [B,Hkv,Sk,D], lse [B,Hq,Sq].  P = exp(s*scale
+    - lse), delta = rowsum(dout*o), dS = P o (dP - delta); dV = P^T.dO,
+    dK = scale * dS^T.Q (both summed over the GQA group), dQ = scale * dS.K.
+    Returns (dq, dk, dv) in the working precision (fp64 for fp64 inputs).
+
+    emulate_bf16=True rounds exactly where the kernel rounds: P and dS to
+    bf16 before their products, the outputs to bf16 (returned widened).  The
+    caller passes bf16-representable q/k/v/o/dout for a faithful yardstick."""
+    B, Hq, Sq, D = q.shape
+    Hkv, Sk = k.shape[1], k.shape[2]
+    G = Hq // Hkv
+    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    wd = torch.float64 if q.dtype is torch.float64 else torch.float32
+
+    def rnd(t):
+        return t.to(torch.bfloat16).to(wd) if emulate_bf16 else t
+
+    qg = _wide(q).reshape(B, Hkv, G, Sq, D)
+    og = o.to(wd).reshape(B, Hkv, G, Sq, D)
+    dog = dout.to(wd).reshape(B, Hkv, G, Sq, D)
+    kg = _wide(k).unsqueeze(2)  # [B,Hkv,1,Sk,D]
+    vg = _wide(v).unsqueeze(2)
+    s = _masked_scores(q, k, causal, scale)
+    p = torch.exp(s - lse.to(wd).reshape(B, Hkv, G, Sq, 1))  # masked -> 0
+    delta = (dog * og).sum(-1, keepdim=True)
+    dp = torch.matmul(dog, vg.transpose(-1, -2))
+    ds = rnd(p * (dp - delta))
+    p = rnd(p)
+    dv = torch.matmul(p.transpose(-1, -2), dog).sum(2)
+    dk = torch.matmul(ds.transpose(-1, -2), qg).sum(2) * scale
+    dq = (torch.matmul(ds, kg) * scale).reshape(B, Hq, Sq, D)
+    return rnd(dq), rnd(dk), rnd(dv)
 
 
 def paged_decode_ref(q, k_cache, v_cache, block_table, seq_lens, block_size,

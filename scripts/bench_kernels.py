@@ -53,6 +53,49 @@ def bench_attention(results):
                                    "pct_peak": round(100 * tf / MFMA_CEIL_TF, 1)}
 
 
+def bench_attention_bwd(results):
+    """Forward+backward through F.attention: the HIP backward against the
+    same call under MODAL_AMD_ATTN_BWD=ref (differentiable reference math,
+    the behaviour before the backward kernel existed).  FLOPs: 4*B*Hq*Sq*Sk*D
+    forward + 10*... backward, halved under the causal mask."""
+    shapes = [
+        ("sdxl_self_s1024_d64", 3, 10, 10, 1024, 1024, 64, False),
+        ("sdxl_self_s256_d64", 3, 20, 20, 256, 256, 64, False),
+        ("sdxl_cross_s1024_kv77", 3, 10, 10, 1024, 77, 64, False),
+        ("llama_gqa_s2048_d128", 4, 32, 8, 2048, 2048, 128, True),
+    ]
+    for name, B, Hq, Hkv, Sq, Sk, D, causal in shapes:
+        q, k, v = (torch.randn(B, h, s, D, device="cuda", dtype=torch.bfloat16,
+                               requires_grad=True)
+                   for h, s in ((Hq, Sq), (Hkv, Sk), (Hkv, Sk)))
+        dout = torch.randn(B, Hq, Sq, D, device="cuda", dtype=torch.bfloat16)
+
+        def step():
+            q.grad = k.grad = v.grad = None
+            F.attention(q, k, v, causal=causal).backward(dout)
+
+        flops = 14.0 * B * Hq * Sq * Sk * D * (0.5 if causal else 1.0)
+        saved = os.environ.pop("MODAL_AMD_ATTN_BWD", None)
+        for path in ("hip", "ref"):
+            if path == "ref":
+                os.environ["MODAL_AMD_ATTN_BWD"] = "ref"
+            torch.cuda.synchronize()
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            dt = timeit(step, iters=200 if Sq * Sk <= 1 << 20 else 50,
+                        warmup=10)
+            peak = torch.cuda.max_memory_allocated() - base
+            tf = flops / dt / 1e12
+            results[f"attn_fwd_bwd/{name}/{path}"] = {
+                "ms": round(dt * 1e3, 3), "TF": round(tf, 1),
+                "pct_peak": round(100 * tf / MFMA_CEIL_TF, 1),
+                "peak_MB": round(peak / 2**20, 1)}
+        os.environ.pop("MODAL_AMD_ATTN_BWD", None)
+        if saved is not None:
+            os.environ["MODAL_AMD_ATTN_BWD"] = saved
+        q.grad = k.grad = v.grad = None
+
+
 def bench_decode(results):
     for name, B, Hq, Hkv, S, D in [
         ("llama_b64_s1024", 64, 32, 8, 1024, 128),
@@ -128,13 +171,19 @@ def bench_gemm_reference(results):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default="")
+    ap.add_argument("--only", default="",
+                    help="comma-separated groups: attention, attention_bwd, "
+                         "decode, memory_ops, gemm_reference (default: all)")
     args = ap.parse_args()
     assert torch.cuda.is_available()
+    groups = {"attention": bench_attention,
+              "attention_bwd": bench_attention_bwd,
+              "decode": bench_decode, "memory_ops": bench_memory_ops,
+              "gemm_reference": bench_gemm_reference}
+    only = [g for g in args.only.split(",") if g] or list(groups)
     results = {}
-    bench_attention(results)
-    bench_decode(results)
-    bench_memory_ops(results)
-    bench_gemm_reference(results)
+    for g in only:
+        groups[g](results)
     text = json.dumps(results, indent=1)
     print(text)
     if args.out:

@@ -22,6 +22,11 @@ OCCUPANCY_FLOORS = {
     "fa32_kernelILi64ELb1": 3,   # D=64 causal
     "fa32_kernelILi64ELb0": 3,   # D=64
     "fa32_kernelILi128ELb1": 2,  # D=128 causal (llama prefill)
+    "fa_bwd_dq_kernelILi64E": 3,     # backward dQ, D=64
+    "fa_bwd_dq_kernelILi128E": 2,    # backward dQ, D=128
+    "fa_bwd_dkdv_kernelILi64E": 2,   # backward dK/dV, D=64
+    "fa_bwd_dkdv_kernelILi128E": 1,  # dK^T+dV^T accumulators take 128 AGPRs
+    "fa_bwd_delta_kernel": 8,
     "decode_kernel": 2,
     "decode_merge_kernel": 4,
 }
