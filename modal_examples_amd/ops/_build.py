@@ -75,7 +75,7 @@ def build(verbose: bool = False, force: bool = False) -> Path:
     common = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC",
               f"-I{CSRC}"]
     objs = []
-    hdr_m = _mtime(CSRC / "common.h")
+    hdr_m = max(_mtime(h) for h in CSRC.glob("*.h"))  # any header rebuilds all
     relink = force or not SO_PATH.exists()
     for src in HIP_SOURCES:
         sp = CSRC / src

@@ -19,103 +19,24 @@
 // before their products, outputs to bf16 — reference.attention_bwd_ref with
 // emulate_bf16=True rounds at the same places.
 //
-// Operand recipe (all of it the forward's, see the top of attention_fwd32.hip
-// for the measured lane semantics):
+// Operand recipe: all of it is the forward's, and both files take it from
+// attention_mfma32.h (tile image, row_frag / tr_frag reads, c8_to_bfrag):
 //   dkdv: S = Q.K^T and dP = dO.V^T with the KEY on the lane (A = a row read
 //     of the Q / dO LDS image, B = this lane's K / V row held in registers).
 //     The C fragments (rows = query in registers, column = key on the lane)
-//     become natural-k-order B operands by cvt_pk_bf16 + permlane32_swap,
-//     exactly as the forward turns P into the B operand of P.V, and feed
+//     become natural-k-order B operands exactly as the forward turns P into
+//     the B operand of P.V, and feed
 //       dV^T += dO^T . P      dK^T += Q^T . dS
-//     whose A operands dO^T / Q^T come from the SAME LDS image by
-//     ds_read_b64_tr_b16 (the forward's V^T read).
+//     whose A operands dO^T / Q^T are transposed reads of the SAME LDS image.
 //   dq: S^T = K.Q^T and dP^T = V.dO^T with the QUERY on the lane (Q and dO
 //     rows in registers), dS^T = P^T o (dP^T - delta) lane-local, and
 //       dQ^T += K^T . dS^T
 //     with K^T read transposed from the K tile where the forward reads V^T.
-#include "common.h"
+#include "attention_mfma32.h"
 
-#define FAB_NWAVES 4
-#define FAB_PPAD 8
-#define FAB_BLK 32  // rows per LDS tile: kv rows (dq) / query rows (dkdv)
-
-typedef __attribute__((ext_vector_type(16))) float fab_f32x16;
-typedef __attribute__((ext_vector_type(4))) short fab_bf16x4;
-typedef __attribute__((address_space(3))) fab_bf16x4* fab_lds_tr_ptr;
-typedef __attribute__((ext_vector_type(2))) int fab_i32x2;
-
-DEV_INLINE int fab_swz(int row, int byte_off) {
-  return byte_off ^ (((row >> 3) & 3) << 4);
-}
-
-DEV_INLINE unsigned fab_cvt_pk_bf16(float lo, float hi) {
-  unsigned r;
-  asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
-}
-
-// element strides of the [B,H,S,D]-logical, d-contiguous tensors
-struct FABwdStrides {
-  long long qb, qh, qs, kb, kh, ks, vb, vh, vs, ob, oh, os;
-  long long gb, gh, gs;  // dO
-  long long dqb, dqh, dqs, dkb, dkh, dks, dvb, dvh, dvs;
-};
-
-// row of a 32x32 C fragment held in register r by lane half hi5
-DEV_INLINE int fab_crow(int r, int hi5) {
-  return (r & 3) + 8 * (r >> 2) + 4 * hi5;
-}
-
-// Row read of a [FAB_BLK][D+PPAD] swizzled tile as the A operand of a
-// 32x32x16 MFMA: lane holds T[l31][c*16 + hi5*8 + j].
-template <int KROW>
-DEV_INLINE bf16x8 fab_row_frag(const short* tile, int l31, int hi5, int c) {
-  return *(const bf16x8*)((const char*)tile + l31 * (KROW * 2) +
-                          fab_swz(l31, (c * 16 + hi5 * 8) * 2));
-}
-
-// Transposed read of the same tile as the A operand T^T: lane holds
-// T[c*16 + hi5*8 + j][dt*32 + l31] (the forward's V^T read).
-template <int KROW>
-DEV_INLINE bf16x8 fab_tr_frag(const short* tile, int l, int hi5, int c,
-                              int dt) {
-  int row0 = c * 16 + hi5 * 8 + ((l & 15) >> 2);
-  int dbase = dt * 32 + ((l >> 4) & 1) * 16 + ((l & 3) * 4);
-  fab_bf16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((fab_lds_tr_ptr)(
-      (char*)tile + row0 * (KROW * 2) + fab_swz(row0, dbase * 2)));
-  fab_bf16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((fab_lds_tr_ptr)(
-      (char*)tile + (row0 + 4) * (KROW * 2) + fab_swz(row0 + 4, dbase * 2)));
-  bf16x8 f;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    f[j] = lo[j];
-    f[j + 4] = hi[j];
-  }
-  return f;
-}
-
-// C fragment (rows in registers) -> the two natural-k-order bf16 B fragments
-// of the 16-row chunks 0 and 1 (the forward's P recipe).
-DEV_INLINE void fab_acc_to_bfrag(const fab_f32x16& x, bf16x8 out[2]) {
-#pragma unroll
-  for (int c = 0; c < 2; ++c) {
-    int pk01 = (int)fab_cvt_pk_bf16(x[c * 8 + 0], x[c * 8 + 1]);
-    int pk23 = (int)fab_cvt_pk_bf16(x[c * 8 + 2], x[c * 8 + 3]);
-    int pk45 = (int)fab_cvt_pk_bf16(x[c * 8 + 4], x[c * 8 + 5]);
-    int pk67 = (int)fab_cvt_pk_bf16(x[c * 8 + 6], x[c * 8 + 7]);
-    fab_i32x2 a = __builtin_amdgcn_permlane32_swap(pk01, pk45, false, false);
-    fab_i32x2 b = __builtin_amdgcn_permlane32_swap(pk23, pk67, false, false);
-    union {
-      int w[4];
-      bf16x8 v;
-    } u;
-    u.w[0] = a[0];
-    u.w[1] = b[0];
-    u.w[2] = a[1];
-    u.w[3] = b[1];
-    out[c] = u.v;
-  }
-}
+#define FA_BWD_NWAVES 4
+#define FA_BWD_BLK 32  // rows per LDS tile: kv rows (dq) / query rows (dkdv)
+#define FA_BWD_NT (FA_BWD_NWAVES * WAVE)
 
 // ------------------------------------------------------------------ delta
 // delta[b,h,q] = sum_d dO[b,h,q,d] * O[b,h,q,d], one wave per 32 rows, as
@@ -124,9 +45,9 @@ DEV_INLINE void fab_acc_to_bfrag(const fab_f32x16& x, bf16x8 out[2]) {
 // below, so the cancellation in dP - delta sees two sums rounded alike — a
 // row that attends to a single key (o == v) gets dS == 0 exactly.
 template <int D>
-__global__ __launch_bounds__(FAB_NWAVES * WAVE) void fa_bwd_delta_kernel(
+__global__ __launch_bounds__(FA_BWD_NT) void fa_bwd_delta_kernel(
     const short* __restrict__ O, const short* __restrict__ dO,
-    float* __restrict__ delta, int Hq, int Sq, FABwdStrides st) {
+    float* __restrict__ delta, int Hq, int Sq, AttnBwdStrides st) {
   constexpr int DCH = D / 16;
   const int w = threadIdx.x / WAVE;
   const int l = threadIdx.x % WAVE;
@@ -134,24 +55,24 @@ __global__ __launch_bounds__(FAB_NWAVES * WAVE) void fa_bwd_delta_kernel(
   const int hi5 = l >> 5;
   const int h = blockIdx.y;
   const int b = blockIdx.z;
-  const int my_q = blockIdx.x * (32 * FAB_NWAVES) + w * 32 + l31;
+  const int my_q = blockIdx.x * (32 * FA_BWD_NWAVES) + w * 32 + l31;
   const bool q_ok = my_q < Sq;
-  const long long oro = b * st.ob + h * st.oh + (long long)my_q * st.os;
-  const long long gro = b * st.gb + h * st.gh + (long long)my_q * st.gs;
-  fab_f32x16 acc;
+  const long long oro = b * st.o.b + h * st.o.h + (long long)my_q * st.o.s;
+  const long long gro = b * st.g.b + h * st.g.h + (long long)my_q * st.g.s;
+  f32x16 acc;
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc[r] = 0.f;
 #pragma unroll
   for (int c = 0; c < DCH; ++c) {
-    bf16x8 of = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-    bf16x8 gf = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+    bf16x8 of = bf16x8_zero();
+    bf16x8 gf = bf16x8_zero();
     if (q_ok) {
       of = *(const bf16x8*)&O[oro + c * 16 + hi5 * 8];
       gf = *(const bf16x8*)&dO[gro + c * 16 + hi5 * 8];
     }
     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gf, of, acc, 0, 0, 0);
   }
-  // C[row = fab_crow(r, hi5)][col = l31]: the diagonal element of column l31
+  // C[row = c_row(r, hi5)][col = l31]: the diagonal element of column l31
   // sits in the lane half hi5 == bit 2 of l31, register (l31&3) + 4*(l31>>3)
   const int rsel = (l31 & 3) + 4 * (l31 >> 3);
   float dsum = 0.f;
@@ -163,21 +84,21 @@ __global__ __launch_bounds__(FAB_NWAVES * WAVE) void fa_bwd_delta_kernel(
 
 // ------------------------------------------------------------------ dK, dV
 template <int D, bool CAUSAL>
-__global__ __launch_bounds__(FAB_NWAVES * WAVE) void fa_bwd_dkdv_kernel(
+__global__ __launch_bounds__(FA_BWD_NT) void fa_bwd_dkdv_kernel(
     const short* __restrict__ Q, const short* __restrict__ K,
     const short* __restrict__ V, const short* __restrict__ dO,
     const float* __restrict__ LSE, const float* __restrict__ DELTA,
     short* __restrict__ dK, short* __restrict__ dV, int B, int Hq, int Hkv,
-    int Sq, int Sk, float scale, FABwdStrides st) {
-  constexpr int KROW = D + FAB_PPAD;
+    int Sq, int Sk, float scale, AttnBwdStrides st) {
+  constexpr int KROW = D + FA_PPAD;
   constexpr int DCH = D / 16;
   constexpr int DT = D / 32;
-  constexpr int KBLK = 32 * FAB_NWAVES;  // keys per workgroup
+  constexpr int KBLK = 32 * FA_BWD_NWAVES;  // keys per workgroup
 
-  __shared__ alignas(16) short Qs[FAB_BLK][KROW];
-  __shared__ alignas(16) short Gs[FAB_BLK][KROW];  // dO
-  __shared__ alignas(16) float lse_s[FAB_BLK];
-  __shared__ alignas(16) float delta_s[FAB_BLK];
+  __shared__ alignas(16) short Qs[FA_BWD_BLK][KROW];
+  __shared__ alignas(16) short Gs[FA_BWD_BLK][KROW];  // dO
+  __shared__ alignas(16) float lse_s[FA_BWD_BLK];
+  __shared__ alignas(16) float delta_s[FA_BWD_BLK];
 
   const int tid = threadIdx.x;
   const int w = tid / WAVE;
@@ -196,21 +117,21 @@ __global__ __launch_bounds__(FAB_NWAVES * WAVE) void fa_bwd_dkdv_kernel(
   // this lane's K and V rows: the B operands of S = Q.K^T and dP = dO.V^T
   bf16x8 kreg[DCH], vreg[DCH];
   {
-    const long long kro = b * st.kb + hkv * st.kh + (long long)my_k * st.ks;
-    const long long vro = b * st.vb + hkv * st.vh + (long long)my_k * st.vs;
+    const long long kro = b * st.k.b + hkv * st.k.h + (long long)my_k * st.k.s;
+    const long long vro = b * st.v.b + hkv * st.v.h + (long long)my_k * st.v.s;
 #pragma unroll
     for (int c = 0; c < DCH; ++c) {
       if (k_ok) {
         kreg[c] = *(const bf16x8*)&K[kro + c * 16 + hi5 * 8];
         vreg[c] = *(const bf16x8*)&V[vro + c * 16 + hi5 * 8];
       } else {
-        kreg[c] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-        vreg[c] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+        kreg[c] = bf16x8_zero();
+        vreg[c] = bf16x8_zero();
       }
     }
   }
 
-  fab_f32x16 dk[DT], dv[DT];
+  f32x16 dk[DT], dv[DT];
 #pragma unroll
   for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
@@ -221,36 +142,23 @@ __global__ __launch_bounds__(FAB_NWAVES * WAVE) void fa_bwd_dkdv_kernel(
 
   // query slices of 32 rows; under the causal mask slices wholly above the
   // diagonal of this key block (last row + causal_off < k0) are skipped
-  const int nqb = (Sq + FAB_BLK - 1) / FAB_BLK;
+  const int nqb = (Sq + FA_BWD_BLK - 1) / FA_BWD_BLK;
   int qb_start = 0;
-  if (CAUSAL && k0 - causal_off > 0) qb_start = (k0 - causal_off) / FAB_BLK;
+  if (CAUSAL && k0 - causal_off > 0) qb_start = (k0 - causal_off) / FA_BWD_BLK;
   const int nsl = nqb > qb_start ? nqb - qb_start : 0;
   const int total = G * nsl;  // (head of the group, slice), heads outermost
 
-  constexpr int CPR = D / 8;
-  constexpr int CPT = (FAB_BLK * CPR) / (FAB_NWAVES * WAVE);
-  bf16x8 qst[CPT], gst[CPT];
+  bf16x8 qst[FA_BWD_BLK * (D / 8) / FA_BWD_NT];
+  bf16x8 gst[FA_BWD_BLK * (D / 8) / FA_BWD_NT];
   float lse_st = 0.f, delta_st = 0.f;
   auto load_slice = [&](int it) {
     const int g = it / nsl;
-    const int q0 = (qb_start + it % nsl) * FAB_BLK;
+    const int q0 = (qb_start + it % nsl) * FA_BWD_BLK;
     const int h = hkv * G + g;
-    const long long qoff = b * st.qb + h * st.qh;
-    const long long goff = b * st.gb + h * st.gh;
-#pragma unroll
-    for (int i = 0; i < CPT; ++i) {
-      int ci = i * FAB_NWAVES * WAVE + tid;
-      int row = ci / CPR, c8 = ci % CPR;
-      int qp = q0 + row;
-      if (qp < Sq) {
-        qst[i] = *(const bf16x8*)&Q[qoff + (long long)qp * st.qs + c8 * 8];
-        gst[i] = *(const bf16x8*)&dO[goff + (long long)qp * st.gs + c8 * 8];
-      } else {
-        qst[i] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-        gst[i] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-      }
-    }
-    if (tid < FAB_BLK) {
+    stage_load<D, FA_BWD_BLK, FA_BWD_NT>(
+        Q + (b * st.q.b + h * st.q.h), st.q.s, dO + (b * st.g.b + h * st.g.h),
+        st.g.s, q0, Sq, tid, qst, gst);
+    if (tid < FA_BWD_BLK) {
       int qp = q0 + tid;
       bool ok = qp < Sq;
       long long ro = ((long long)b * Hq + h) * Sq + qp;
@@ -259,15 +167,9 @@ __global__ __launch_bounds__(FAB_NWAVES * WAVE) void fa_bwd_dkdv_kernel(
     }
   };
   auto write_slice = [&]() {
-#pragma unroll
-    for (int i = 0; i < CPT; ++i) {
-      int ci = i * FAB_NWAVES * WAVE + tid;
-      int row = ci / CPR, c8 = ci % CPR;
-      int boff = fab_swz(row, c8 * 16);
-      *(bf16x8*)((char*)&Qs[row][0] + boff) = qst[i];
-      *(bf16x8*)((char*)&Gs[row][0] + boff) = gst[i];
-    }
-    if (tid < FAB_BLK) {
+    stage_write<D, FA_BWD_BLK, FA_BWD_NT>(&Qs[0][0], &Gs[0][0], tid, qst,
+                                          gst);
+    if (tid < FA_BWD_BLK) {
       lse_s[tid] = lse_st;
       delta_s[tid] = delta_st;
     }
@@ -275,14 +177,14 @@ __global__ __launch_bounds__(FAB_NWAVES * WAVE) void fa_bwd_dkdv_kernel(
 
   if (total > 0) load_slice(0);
   for (int it = 0; it < total; ++it) {
-    const int q0 = (qb_start + it % nsl) * FAB_BLK;
+    const int q0 = (qb_start + it % nsl) * FA_BWD_BLK;
     __syncthreads();
     write_slice();
     __syncthreads();
     if (it + 1 < total) load_slice(it + 1);
 
     // ---- S = Q.K^T, dP = dO.V^T: rows = query (registers), col = key ----
-    fab_f32x16 s, dp;
+    f32x16 s, dp;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       s[r] = 0.f;
@@ -290,8 +192,8 @@ __global__ __launch_bounds__(FAB_NWAVES * WAVE) void fa_bwd_dkdv_kernel(
     }
 #pragma unroll
     for (int c = 0; c < DCH; ++c) {
-      bf16x8 qf = fab_row_frag<KROW>(&Qs[0][0], l31, hi5, c);
-      bf16x8 gf = fab_row_frag<KROW>(&Gs[0][0], l31, hi5, c);
+      bf16x8 qf = row_frag<KROW>(&Qs[0][0], l31, hi5, c);
+      bf16x8 gf = row_frag<KROW>(&Gs[0][0], l31, hi5, c);
       s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qf, kreg[c], s, 0, 0, 0);
       dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gf, vreg[c], dp, 0, 0, 0);
     }
@@ -304,7 +206,7 @@ __global__ __launch_bounds__(FAB_NWAVES * WAVE) void fa_bwd_dkdv_kernel(
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         int r = 4 * g4 + j;
-        int qp = q0 + 8 * g4 + 4 * hi5 + j;  // == q0 + fab_crow(r, hi5)
+        int qp = q0 + 8 * g4 + 4 * hi5 + j;  // == q0 + c_row(r, hi5)
         bool dead = !k_ok || qp >= Sq || (CAUSAL && my_k > qp + causal_off);
         float p = dead ? 0.f : __expf(s[r] * scale - lse4[j]);
         s[r] = p;
@@ -312,16 +214,19 @@ __global__ __launch_bounds__(FAB_NWAVES * WAVE) void fa_bwd_dkdv_kernel(
       }
     }
     bf16x8 pfrag[2], dsfrag[2];
-    fab_acc_to_bfrag(s, pfrag);
-    fab_acc_to_bfrag(dp, dsfrag);
+#pragma unroll
+    for (int c = 0; c < 2; ++c) {
+      pfrag[c] = c8_to_bfrag((const float*)&s + c * 8);
+      dsfrag[c] = c8_to_bfrag((const float*)&dp + c * 8);
+    }
 
     // ---- dV^T += dO^T . P ; dK^T += Q^T . dS ----
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) {
-        bf16x8 gt = fab_tr_frag<KROW>(&Gs[0][0], l, hi5, c, dt);
-        bf16x8 qt = fab_tr_frag<KROW>(&Qs[0][0], l, hi5, c, dt);
+        bf16x8 gt = tr_frag<KROW>(&Gs[0][0], l, hi5, c, dt);
+        bf16x8 qt = tr_frag<KROW>(&Qs[0][0], l, hi5, c, dt);
         dv[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(gt, pfrag[c], dv[dt],
                                                          0, 0, 0);
         dk[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qt, dsfrag[c], dk[dt],
@@ -333,14 +238,14 @@ __global__ __launch_bounds__(FAB_NWAVES * WAVE) void fa_bwd_dkdv_kernel(
   // ---- epilogue: dK[key][d] = scale * dK^T[d][key], dV[key][d] ----
   if (k_ok) {
     const long long dko =
-        b * st.dkb + hkv * st.dkh + (long long)my_k * st.dks;
+        b * st.dk.b + hkv * st.dk.h + (long long)my_k * st.dk.s;
     const long long dvo =
-        b * st.dvb + hkv * st.dvh + (long long)my_k * st.dvs;
+        b * st.dv.b + hkv * st.dv.h + (long long)my_k * st.dv.s;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        int d = dt * 32 + fab_crow(r, hi5);
+        int d = dt * 32 + c_row(r, hi5);
         dK[dko + d] = f2bf(dk[dt][r] * scale);
         dV[dvo + d] = f2bf(dv[dt][r]);
       }
@@ -349,17 +254,17 @@ __global__ __launch_bounds__(FAB_NWAVES * WAVE) void fa_bwd_dkdv_kernel(
 
 // ------------------------------------------------------------------ dQ
 template <int D, bool CAUSAL>
-__global__ __launch_bounds__(FAB_NWAVES * WAVE) void fa_bwd_dq_kernel(
+__global__ __launch_bounds__(FA_BWD_NT) void fa_bwd_dq_kernel(
     const short* __restrict__ Q, const short* __restrict__ K,
     const short* __restrict__ V, const short* __restrict__ dO,
     const float* __restrict__ LSE, const float* __restrict__ DELTA,
     short* __restrict__ dQ, int B, int Hq, int Hkv, int Sq, int Sk,
-    float scale, FABwdStrides st) {
-  constexpr int KROW = D + FAB_PPAD;
+    float scale, AttnBwdStrides st) {
+  constexpr int KROW = D + FA_PPAD;
   constexpr int DCH = D / 16;
   constexpr int DT = D / 32;
-  constexpr int QBLK = 32 * FAB_NWAVES;
-  constexpr int KVB = FAB_BLK;
+  constexpr int QBLK = 32 * FA_BWD_NWAVES;
+  constexpr int KVB = FA_BWD_BLK;
 
   __shared__ alignas(16) short Ks[KVB][KROW];
   __shared__ alignas(16) short Vs[KVB][KROW];
@@ -375,8 +280,8 @@ __global__ __launch_bounds__(FAB_NWAVES * WAVE) void fa_bwd_dq_kernel(
   const int b = blockIdx.z;
   const int hkv = h / (Hq / Hkv);
 
-  const long long koff = b * st.kb + hkv * st.kh;
-  const long long voff = b * st.vb + hkv * st.vh;
+  const long long koff = b * st.k.b + hkv * st.k.h;
+  const long long voff = b * st.v.b + hkv * st.v.h;
   const int my_q = qblk * QBLK + w * 32 + l31;  // this lane's query row
   const bool q_ok = my_q < Sq;
   const int causal_off = Sk - Sq;
@@ -385,16 +290,16 @@ __global__ __launch_bounds__(FAB_NWAVES * WAVE) void fa_bwd_dq_kernel(
   bf16x8 qreg[DCH], greg[DCH];
   float lse_q = 0.f, delta_q = 0.f;
   {
-    const long long qro = b * st.qb + h * st.qh + (long long)my_q * st.qs;
-    const long long gro = b * st.gb + h * st.gh + (long long)my_q * st.gs;
+    const long long qro = b * st.q.b + h * st.q.h + (long long)my_q * st.q.s;
+    const long long gro = b * st.g.b + h * st.g.h + (long long)my_q * st.g.s;
 #pragma unroll
     for (int c = 0; c < DCH; ++c) {
       if (q_ok) {
         qreg[c] = *(const bf16x8*)&Q[qro + c * 16 + hi5 * 8];
         greg[c] = *(const bf16x8*)&dO[gro + c * 16 + hi5 * 8];
       } else {
-        qreg[c] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-        greg[c] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+        qreg[c] = bf16x8_zero();
+        greg[c] = bf16x8_zero();
       }
     }
     if (q_ok) {
@@ -404,7 +309,7 @@ __global__ __launch_bounds__(FAB_NWAVES * WAVE) void fa_bwd_dq_kernel(
     }
   }
 
-  fab_f32x16 acc[DT];
+  f32x16 acc[DT];
 #pragma unroll
   for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
@@ -417,33 +322,13 @@ __global__ __launch_bounds__(FAB_NWAVES * WAVE) void fa_bwd_dq_kernel(
     if (lim < nkb) nkb = lim;
   }
 
-  constexpr int CPR = D / 8;
-  constexpr int CPT = (KVB * CPR) / (FAB_NWAVES * WAVE);
-  bf16x8 kst[CPT], vst[CPT];
+  bf16x8 kst[KVB * (D / 8) / FA_BWD_NT], vst[KVB * (D / 8) / FA_BWD_NT];
   auto load_chunks = [&](int kb) {
-#pragma unroll
-    for (int i = 0; i < CPT; ++i) {
-      int ci = i * FAB_NWAVES * WAVE + tid;
-      int row = ci / CPR, c8 = ci % CPR;
-      int kvp = kb * KVB + row;
-      if (kvp < Sk) {
-        kst[i] = *(const bf16x8*)&K[koff + (long long)kvp * st.ks + c8 * 8];
-        vst[i] = *(const bf16x8*)&V[voff + (long long)kvp * st.vs + c8 * 8];
-      } else {
-        kst[i] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-        vst[i] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-      }
-    }
+    stage_load<D, KVB, FA_BWD_NT>(K + koff, st.k.s, V + voff, st.v.s,
+                                  kb * KVB, Sk, tid, kst, vst);
   };
   auto write_chunks = [&]() {
-#pragma unroll
-    for (int i = 0; i < CPT; ++i) {
-      int ci = i * FAB_NWAVES * WAVE + tid;
-      int row = ci / CPR, c8 = ci % CPR;
-      int boff = fab_swz(row, c8 * 16);
-      *(bf16x8*)((char*)&Ks[row][0] + boff) = kst[i];
-      *(bf16x8*)((char*)&Vs[row][0] + boff) = vst[i];
-    }
+    stage_write<D, KVB, FA_BWD_NT>(&Ks[0][0], &Vs[0][0], tid, kst, vst);
   };
 
   if (nkb > 0) load_chunks(0);
@@ -454,7 +339,7 @@ __global__ __launch_bounds__(FAB_NWAVES * WAVE) void fa_bwd_dq_kernel(
     if (kb + 1 < nkb) load_chunks(kb + 1);
 
     // ---- S^T = K.Q^T, dP^T = V.dO^T: rows = key (registers), col = query
-    fab_f32x16 s, dp;
+    f32x16 s, dp;
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
       s[r] = 0.f;
@@ -462,8 +347,8 @@ __global__ __launch_bounds__(FAB_NWAVES * WAVE) void fa_bwd_dq_kernel(
     }
 #pragma unroll
     for (int c = 0; c < DCH; ++c) {
-      bf16x8 kf = fab_row_frag<KROW>(&Ks[0][0], l31, hi5, c);
-      bf16x8 vf = fab_row_frag<KROW>(&Vs[0][0], l31, hi5, c);
+      bf16x8 kf = row_frag<KROW>(&Ks[0][0], l31, hi5, c);
+      bf16x8 vf = row_frag<KROW>(&Vs[0][0], l31, hi5, c);
       s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qreg[c], s, 0, 0, 0);
       dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, greg[c], dp, 0, 0, 0);
     }
@@ -471,20 +356,22 @@ __global__ __launch_bounds__(FAB_NWAVES * WAVE) void fa_bwd_dq_kernel(
     // ---- dS^T = P^T o (dP^T - delta); masked -> 0 ----
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-      int kvp = kb * KVB + fab_crow(r, hi5);
+      int kvp = kb * KVB + c_row(r, hi5);
       bool dead = !q_ok || kvp >= Sk || (CAUSAL && kvp > my_q + causal_off);
       float p = dead ? 0.f : __expf(s[r] * scale - lse_q);
       dp[r] = p * (dp[r] - delta_q);
     }
     bf16x8 dsfrag[2];
-    fab_acc_to_bfrag(dp, dsfrag);
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+      dsfrag[c] = c8_to_bfrag((const float*)&dp + c * 8);
 
     // ---- dQ^T += K^T . dS^T (K^T via transposed reads of the K tile) ----
 #pragma unroll
     for (int c = 0; c < 2; ++c) {
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) {
-        bf16x8 kt = fab_tr_frag<KROW>(&Ks[0][0], l, hi5, c, dt);
+        bf16x8 kt = tr_frag<KROW>(&Ks[0][0], l, hi5, c, dt);
         acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kt, dsfrag[c],
                                                           acc[dt], 0, 0, 0);
       }
@@ -493,21 +380,20 @@ __global__ __launch_bounds__(FAB_NWAVES * WAVE) void fa_bwd_dq_kernel(
 
   // ---- epilogue: dQ[q][d] = scale * dQ^T[d][q] ----
   if (q_ok) {
-    const long long dqo = b * st.dqb + h * st.dqh + (long long)my_q * st.dqs;
+    const long long dqo = b * st.dq.b + h * st.dq.h + (long long)my_q * st.dq.s;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        int d = dt * 32 + fab_crow(r, hi5);
+        int d = dt * 32 + c_row(r, hi5);
         dQ[dqo + d] = f2bf(acc[dt][r] * scale);
       }
   }
 }
 
 // q/k/v/o/dout and dq/dk/dv are logically [B,H,S,D] with d contiguous;
-// strides[24] holds the element strides (batch, head, sequence) of
-// q k v o dout dq dk dv in that order.  lse and delta are fp32 [B,Hq,Sq]
-// contiguous; delta is scratch that the preprocess kernel fills.  Returns 0
+// strides[24] is the flat image of AttnBwdStrides (q k v o dout dq dk dv).
+// lse and delta are fp32 [B,Hq,Sq] contiguous; delta is scratch that the preprocess kernel fills.  Returns 0
 // once the three kernels are launched, non-zero (nothing launched) for an
 // unsupported configuration: D must be 64 or 128, Hq a multiple of Hkv,
 // Sq and Sk at least 1, and causal needs Sk >= Sq.
@@ -516,17 +402,9 @@ extern "C" int fa_bwd_strided_bf16(
     const void* dout, const float* lse, float* delta, void* dq, void* dk,
     void* dv, int B, int Hq, int Hkv, int Sq, int Sk, int D, float scale,
     int causal, const long long* strides, hipStream_t stream) {
-  if ((D != 64 && D != 128) || Hkv <= 0 || Hq % Hkv != 0) return 1;
+  if (!attn_mfma32_supported(D, Hq, Hkv)) return 1;
   if (B < 1 || Sq < 1 || Sk < 1 || (causal && Sk < Sq)) return 1;
-  FABwdStrides st;
-  st.qb = strides[0]; st.qh = strides[1]; st.qs = strides[2];
-  st.kb = strides[3]; st.kh = strides[4]; st.ks = strides[5];
-  st.vb = strides[6]; st.vh = strides[7]; st.vs = strides[8];
-  st.ob = strides[9]; st.oh = strides[10]; st.os = strides[11];
-  st.gb = strides[12]; st.gh = strides[13]; st.gs = strides[14];
-  st.dqb = strides[15]; st.dqh = strides[16]; st.dqs = strides[17];
-  st.dkb = strides[18]; st.dkh = strides[19]; st.dks = strides[20];
-  st.dvb = strides[21]; st.dvh = strides[22]; st.dvs = strides[23];
+  const AttnBwdStrides st = attn_strides_from<AttnBwdStrides>(strides);
   const short* Qp = (const short*)q;
   const short* Kp = (const short*)k;
   const short* Vp = (const short*)v;
@@ -536,10 +414,10 @@ extern "C" int fa_bwd_strided_bf16(
   short* dKp = (short*)dk;
   short* dVp = (short*)dv;
 
-  dim3 block(FAB_NWAVES * WAVE);
+  dim3 block(FA_BWD_NT);
   dim3 grid_kv((Sk + 127) / 128, Hkv, B);
   dim3 grid_q((Sq + 127) / 128, Hq, B);
-#define FAB_LAUNCH(DD, CC)                                                    \
+#define FA_BWD_LAUNCH(DD, CC)                                                 \
   do {                                                                        \
     hipLaunchKernelGGL((fa_bwd_delta_kernel<DD>), grid_q, block, 0, stream,   \
                        Op, Gp, delta, Hq, Sq, st);                            \
@@ -551,10 +429,10 @@ extern "C" int fa_bwd_strided_bf16(
                        scale, st);                                            \
   } while (0)
   if (D == 64) {
-    if (causal) FAB_LAUNCH(64, true); else FAB_LAUNCH(64, false);
+    if (causal) FA_BWD_LAUNCH(64, true); else FA_BWD_LAUNCH(64, false);
   } else {
-    if (causal) FAB_LAUNCH(128, true); else FAB_LAUNCH(128, false);
+    if (causal) FA_BWD_LAUNCH(128, true); else FA_BWD_LAUNCH(128, false);
   }
-#undef FAB_LAUNCH
+#undef FA_BWD_LAUNCH
   return 0;
 }

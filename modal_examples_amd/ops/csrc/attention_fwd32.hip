@@ -12,41 +12,18 @@
 //     (C layout col = q = lane&31); row-softmax becomes 15 in-register ops +
 //     ONE shfl_xor(32) to combine with the partner lane.  Rescale factors are
 //     lane-local (no broadcast).
-//   P converts to bf16 B-fragments IN REGISTERS: v_cvt_pk_bf16_f32 pairs +
-//     permlane32_swap half-exchanges (semantics measured: result pair is
-//     (A_lo||B_lo , A_hi||B_hi)) — P never touches LDS.
-//   PV: O^T = V^T · P^T, V^T fragments via ds_read_b64_tr_b16 hardware
-//     transpose reads (4x4 lane-grid exchange, measured in probe_tr16.cpp).
+//   P converts to bf16 B-fragments IN REGISTERS (c8_to_bfrag) — P never
+//     touches LDS.
+//   PV: O^T = V^T · P^T, V^T fragments by hardware transpose reads (tr_frag)
+//     of the same LDS image the K row reads (row_frag) use.
 //
-// Fragment layouts (verified on-device, scripts/probe_mfma32.cpp):
-//   A[m][k]: lane holds A[l&31][(l>>5)*8+j];  B[k][n]: B[(l>>5)*8+j][l&31]
-//   C[m][n]: lane holds C[(reg&3)+8*(reg>>2)+4*(l>>5)][l&31], reg 0..15.
-#include "common.h"
+// Fragment layouts, the LDS tile image and the measured lane semantics of
+// those helpers: attention_mfma32.h, shared with attention_bwd.hip.
+#include "attention_mfma32.h"
 
 #include <cstdlib>
 
 #define FA32_NWAVES 4
-#define FA32_KVBLK 32
-#define FA32_PPAD 8
-
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef __attribute__((ext_vector_type(4))) short bf16x4_v7;
-typedef __attribute__((address_space(3))) bf16x4_v7* lds_tr_ptr7;
-typedef __attribute__((ext_vector_type(2))) int i32x2;
-
-DEV_INLINE int kv_swz7(int row, int byte_off) {
-  return byte_off ^ (((row >> 3) & 3) << 4);
-}
-
-DEV_INLINE unsigned cvt_pk_bf16(float lo, float hi) {
-  unsigned r;
-  asm volatile("v_cvt_pk_bf16_f32 %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi));
-  return r;
-}
-
-struct FA32Strides {
-  long long qb, qh, qs, kb, kh, ks, vb, vh, vs, ob, oh, os;
-};
 
 // KVB: kv rows per block iteration.  64 halves the barrier/softmax rounds
 // per token vs the r1 kernel's 32 (the m214-ladder "KVBLK=64" lever).
@@ -63,8 +40,8 @@ void fa32_kernel(
     const short* __restrict__ Q, const short* __restrict__ K,
     const short* __restrict__ V, short* __restrict__ O,
     float* __restrict__ LSE, int B, int Hq, int Hkv, int Sq, int Sk,
-    float scale, FA32Strides st) {
-  constexpr int KROW = D + FA32_PPAD;
+    float scale, AttnFwdStrides st) {
+  constexpr int KROW = D + FA_PPAD;
   constexpr int DCH = D / 16;  // QK^T k-chunks (K-dim 16)
   constexpr int DT = D / 32;   // PV d-tiles (M-dim 32)
   constexpr int QBLK = 32 * FA32_NWAVES;
@@ -84,10 +61,10 @@ void fa32_kernel(
   const int b = blockIdx.z;
   const int hkv = h / (Hq / Hkv);
 
-  const long long qoff = b * st.qb + h * st.qh;
-  const long long koff = b * st.kb + hkv * st.kh;
-  const long long voff = b * st.vb + hkv * st.vh;
-  const long long ooff = b * st.ob + h * st.oh;
+  const long long qoff = b * st.q.b + h * st.q.h;
+  const long long koff = b * st.k.b + hkv * st.k.h;
+  const long long voff = b * st.v.b + hkv * st.v.h;
+  const long long ooff = b * st.o.b + h * st.o.h;
   const int q0 = qblk * QBLK + w * 32;
   const int my_q = q0 + l31;  // this lane's query row
   const int causal_off = Sk - Sq;
@@ -96,13 +73,13 @@ void fa32_kernel(
   // registers for all D — measured: reloading Q from L2 per KV block instead
   // regressed D=128 by 22-30% (occupancy stayed at 2 waves/SIMD).
   bf16x8 qreg[DCH];
-  const long long qrow_off = qoff + (long long)my_q * st.qs;
+  const long long qrow_off = qoff + (long long)my_q * st.q.s;
   const bool q_ok = my_q < Sq;
 #pragma unroll
   for (int c = 0; c < DCH; ++c) {
     qreg[c] = q_ok
         ? *(const bf16x8*)&Q[qrow_off + c * 16 + hi5 * 8]
-        : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
+        : bf16x8_zero();
   }
 
   f32x16 acc[DT];
@@ -120,33 +97,14 @@ void fa32_kernel(
   }
 
   // async register staging: next block loads issue before this block computes
-  constexpr int CPR = D / 8;
-  constexpr int CPT = (KVB * CPR) / (FA32_NWAVES * WAVE);
-  bf16x8 kreg[CPT], vreg[CPT];
+  constexpr int NT = FA32_NWAVES * WAVE;
+  bf16x8 kreg[KVB * (D / 8) / NT], vreg[KVB * (D / 8) / NT];
   auto load_chunks = [&](int kb) {
-#pragma unroll
-    for (int i = 0; i < CPT; ++i) {
-      int ci = i * FA32_NWAVES * WAVE + tid;
-      int row = ci / CPR, c8 = ci % CPR;
-      int kvp = kb * KVB + row;
-      if (kvp < Sk) {
-        kreg[i] = *(const bf16x8*)&K[koff + kvp * st.ks + c8 * 8];
-        vreg[i] = *(const bf16x8*)&V[voff + kvp * st.vs + c8 * 8];
-      } else {
-        kreg[i] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-        vreg[i] = bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-      }
-    }
+    stage_load<D, KVB, NT>(K + koff, st.k.s, V + voff, st.v.s, kb * KVB, Sk,
+                           tid, kreg, vreg);
   };
   auto write_chunks = [&]() {
-#pragma unroll
-    for (int i = 0; i < CPT; ++i) {
-      int ci = i * FA32_NWAVES * WAVE + tid;
-      int row = ci / CPR, c8 = ci % CPR;
-      int boff = kv_swz7(row, c8 * 16);
-      *(bf16x8*)((char*)&Ks[row][0] + boff) = kreg[i];
-      *(bf16x8*)((char*)&Vs[row][0] + boff) = vreg[i];
-    }
+    stage_write<D, KVB, NT>(&Ks[0][0], &Vs[0][0], tid, kreg, vreg);
   };
 
   load_chunks(0);
@@ -167,9 +125,7 @@ void fa32_kernel(
 #pragma unroll
       for (int c = 0; c < DCH; ++c) {
         // A = K[kv][d]: lane holds K[f*32 + l31][c*16 + hi5*8 + j]
-        int krow = f * 32 + l31;
-        bf16x8 kfrag = *(const bf16x8*)(
-            (char*)&Ks[krow][0] + kv_swz7(krow, (c * 16 + hi5 * 8) * 2));
+        bf16x8 kfrag = row_frag<KROW>(&Ks[0][0], f * 32 + l31, hi5, c);
         __builtin_amdgcn_s_setprio(1);
         s[f] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfrag, qreg[c], s[f], 0,
                                                        0, 0);
@@ -184,7 +140,7 @@ void fa32_kernel(
     for (int f = 0; f < KF; ++f)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        int kvp = kb * KVB + f * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi5;
+        int kvp = kb * KVB + f * 32 + c_row(r, hi5);
         bool dead = !full && ((kvp >= Sk) || (CAUSAL && kvp > my_q + causal_off));
         s[f][r] = dead ? -1e30f : s[f][r] * scale;
       }
@@ -218,50 +174,18 @@ void fa32_kernel(
     psum += __shfl_xor(psum, 32, WAVE);
     l_run = (kb == 0) ? psum : l_run + psum;
 
-    // ---- P → bf16 B-fragments in registers (cvt_pk + permlane32_swap) ----
-    // own regs pack kv pairs; half-exchange composes the 16-kv chunks:
-    //   chunk c frag words = [A'(pk01,pk45), A'(pk23,pk67), B'(same), B'(same)]
+    // ---- P → bf16 B-fragments in registers, one per 16-kv chunk ----
     bf16x8 pfrag[2 * KF];
 #pragma unroll
-    for (int c = 0; c < 2 * KF; ++c) {
-      float* sv = (float*)&s[c >> 1] + (c & 1) * 8;
-      int pk01 = (int)cvt_pk_bf16(sv[0], sv[1]);
-      int pk23 = (int)cvt_pk_bf16(sv[2], sv[3]);
-      int pk45 = (int)cvt_pk_bf16(sv[4], sv[5]);
-      int pk67 = (int)cvt_pk_bf16(sv[6], sv[7]);
-      i32x2 x = __builtin_amdgcn_permlane32_swap(pk01, pk45, false, false);
-      i32x2 y = __builtin_amdgcn_permlane32_swap(pk23, pk67, false, false);
-      union {
-        int w[4];
-        bf16x8 v;
-      } u;
-      u.w[0] = x[0];
-      u.w[1] = y[0];
-      u.w[2] = x[1];
-      u.w[3] = y[1];
-      pfrag[c] = u.v;
-    }
+    for (int c = 0; c < 2 * KF; ++c)
+      pfrag[c] = c8_to_bfrag((const float*)&s[c >> 1] + (c & 1) * 8);
 
-    // ---- O^T += V^T · P^T (V^T via tr16 hardware transpose reads) ----
+    // ---- O^T += V^T · P^T (V^T via hardware transpose reads) ----
 #pragma unroll
     for (int c = 0; c < 2 * KF; ++c) {
 #pragma unroll
       for (int dt = 0; dt < DT; ++dt) {
-        // lane (within its 16-group: 4a+b) issues the source read for
-        // V[c*16 + hi5*8 + (l&15)>>2 .. +4][dt*32 + ((l>>4)&1)*16 + 4a]
-        int row0 = c * 16 + hi5 * 8 + ((l & 15) >> 2);
-        int dbase = dt * 32 + ((l >> 4) & 1) * 16 + ((l & 3) * 4);
-        bf16x4_v7 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_ptr7)(
-            (char*)&Vs[0][0] + row0 * (KROW * 2) + kv_swz7(row0, dbase * 2)));
-        bf16x4_v7 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr_ptr7)(
-            (char*)&Vs[0][0] + (row0 + 4) * (KROW * 2) +
-            kv_swz7(row0 + 4, dbase * 2)));
-        bf16x8 vfrag;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-          vfrag[j] = lo[j];
-          vfrag[j + 4] = hi[j];
-        }
+        bf16x8 vfrag = tr_frag<KROW>(&Vs[0][0], l, hi5, c, dt);
         __builtin_amdgcn_s_setprio(1);
         acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vfrag, pfrag[c],
                                                           acc[dt], 0, 0, 0);
@@ -282,14 +206,14 @@ void fa32_kernel(
     for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
-        int d = dt * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi5;
-        O[ooff + (long long)my_q * st.os + d] = f2bf(acc[dt][r] * inv);
+        int d = dt * 32 + c_row(r, hi5);
+        O[ooff + (long long)my_q * st.o.s + d] = f2bf(acc[dt][r] * inv);
       }
   }
 }
 
-// q/k/v/o are logically [B,H,S,D] with d contiguous; strides[12] holds the
-// element strides qb qh qs kb kh ks vb vh vs ob oh os.  Returns 0 once the
+// q/k/v/o are logically [B,H,S,D] with d contiguous; strides[12] is the flat
+// image of AttnFwdStrides (q k v o).  Returns 0 once the
 // kernel is launched, non-zero (nothing launched) for an unsupported
 // configuration: D must be 64 or 128 and Hq a multiple of Hkv.  lse, when
 // not null, receives the fp32 log-sum-exp per query row, [B,Hq,Sq] contiguous.
@@ -297,16 +221,12 @@ extern "C" int fa32_fwd_strided_bf16(
     const void* q, const void* k, const void* v, void* o, float* lse, int B,
     int Hq, int Hkv, int Sq, int Sk, int D, float scale, int causal,
     const long long* strides, hipStream_t stream) {
-  if ((D != 64 && D != 128) || Hkv <= 0 || Hq % Hkv != 0) return 1;
+  if (!attn_mfma32_supported(D, Hq, Hkv)) return 1;
   const short* Qp = (const short*)q;
   const short* Kp = (const short*)k;
   const short* Vp = (const short*)v;
   short* Op = (short*)o;
-  FA32Strides st;
-  st.qb = strides[0]; st.qh = strides[1]; st.qs = strides[2];
-  st.kb = strides[3]; st.kh = strides[4]; st.ks = strides[5];
-  st.vb = strides[6]; st.vh = strides[7]; st.vs = strides[8];
-  st.ob = strides[9]; st.oh = strides[10]; st.os = strides[11];
+  const AttnFwdStrides st = attn_strides_from<AttnFwdStrides>(strides);
   dim3 grid((Sq + 127) / 128, Hq, B);
   dim3 block(FA32_NWAVES * WAVE);
   // KVB is chosen per head-dim (A/B-measured, profiles/attn_ab_r2.txt):

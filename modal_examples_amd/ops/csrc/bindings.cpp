@@ -87,37 +87,61 @@ void check_bhsd(const torch::Tensor& t, const char* name) {
   TORCH_CHECK(t.stride(3) == 1, name, ": head_dim must be contiguous");
 }
 
-// The one forward-attention launch: q/k/v/o are logically [B,H,S,D] with ANY
-// batch/head/sequence strides (d contiguous), read straight off the tensors.
-// Unsupported configurations raise here, before anything is launched.
-// lse, when not null, receives the fp32 log-sum-exp per query row [B,Hq,Sq].
-void attention_fwd(const torch::Tensor& q, const torch::Tensor& k,
-                   const torch::Tensor& v, const torch::Tensor& o, bool causal,
-                   double scale, float* lse = nullptr) {
+struct AttnDims {
+  int B, Hq, Hkv, Sq, Sk, D;
+};
+
+// The q/k/v checks of both directions; `op` names the entry in the messages.
+AttnDims check_qkv(const char* op, const torch::Tensor& q,
+                   const torch::Tensor& k, const torch::Tensor& v) {
   check_bhsd(q, "q");
   check_bhsd(k, "k");
   check_bhsd(v, "v");
-  int B = q.size(0), Hq = q.size(1), Sq = q.size(2), D = q.size(3);
-  int Hkv = k.size(1), Sk = k.size(2);
-  TORCH_CHECK(D == 64 || D == 128, "attention: unsupported head_dim ", D,
+  AttnDims d{(int)q.size(0), (int)q.size(1), (int)k.size(1), (int)q.size(2),
+             (int)k.size(2), (int)q.size(3)};
+  TORCH_CHECK(d.D == 64 || d.D == 128, op, ": unsupported head_dim ", d.D,
               " (supported: 64, 128)");
-  TORCH_CHECK(k.size(0) == B && k.size(3) == D && v.sizes() == k.sizes(),
-              "attention: k/v must be [B,Hkv,Sk,D] matching q's B and D");
-  TORCH_CHECK(Hkv > 0 && Hq % Hkv == 0, "GQA requires Hq % Hkv == 0, got Hq=",
-              Hq, " Hkv=", Hkv);
-  long long st[12] = {
-      q.stride(0), q.stride(1), q.stride(2),
-      k.stride(0), k.stride(1), k.stride(2),
-      v.stride(0), v.stride(1), v.stride(2),
-      o.stride(0), o.stride(1), o.stride(2),
-  };
-  int rc = fa32_fwd_strided_bf16(q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                                 o.data_ptr(), lse, B, Hq, Hkv, Sq, Sk, D,
-                                 (float)scale, causal ? 1 : 0, st,
-                                 cur_stream());
+  TORCH_CHECK(k.size(0) == d.B && k.size(3) == d.D && v.sizes() == k.sizes(),
+              op, ": k/v must be [B,Hkv,Sk,D] matching q's B and D");
+  TORCH_CHECK(d.Hkv > 0 && d.Hq % d.Hkv == 0,
+              "GQA requires Hq % Hkv == 0, got Hq=", d.Hq, " Hkv=", d.Hkv);
+  return d;
+}
+
+// appends the (batch, head, sequence) element strides of t: one AttnStride
+// of the launchers' flat stride image (csrc/attention_mfma32.h)
+void push_strides(std::vector<long long>& st, const torch::Tensor& t) {
+  st.insert(st.end(), {t.stride(0), t.stride(1), t.stride(2)});
+}
+
+// The one forward-attention launch: q/k/v are logically [B,H,S,D] with ANY
+// batch/head/sequence strides (d contiguous), read straight off the tensors.
+// The output is allocated here, [B,H,S,D] contiguous or, for bshd,
+// [B,S,H,D] contiguous so callers in sequence-major models (UNet/Llama/
+// Whisper blocks) skip every transpose copy around the kernel.  with_lse
+// (training) also returns the fp32 log-sum-exp per query row [B,Hq,Sq] that
+// the backward recomputes P from.  Unsupported configurations raise here,
+// before anything is launched.
+std::tuple<torch::Tensor, torch::Tensor> attention_fwd(
+    const torch::Tensor& q, const torch::Tensor& k, const torch::Tensor& v,
+    bool causal, double scale, bool bshd, bool with_lse) {
+  const AttnDims d = check_qkv("attention", q, k, v);
+  auto o = bshd ? torch::empty({d.B, d.Sq, d.Hq, d.D}, q.options())
+                : torch::empty(q.sizes(), q.options());
+  torch::Tensor lse;
+  if (with_lse)
+    lse = torch::empty({d.B, d.Hq, d.Sq}, q.options().dtype(torch::kFloat32));
+  std::vector<long long> st;
+  for (const auto& t : {q, k, v, bshd ? o.transpose(1, 2) : o})
+    push_strides(st, t);
+  int rc = fa32_fwd_strided_bf16(
+      q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(),
+      with_lse ? lse.data_ptr<float>() : nullptr, d.B, d.Hq, d.Hkv, d.Sq,
+      d.Sk, d.D, (float)scale, causal ? 1 : 0, st.data(), cur_stream());
   TORCH_CHECK(rc == 0, "attention: configuration not supported by the kernel "
               "(head_dim must be 64 or 128 and Hq a multiple of Hkv; got D=",
-              D, " Hq=", Hq, " Hkv=", Hkv, ")");
+              d.D, " Hq=", d.Hq, " Hkv=", d.Hkv, ")");
+  return {o, lse};
 }
 
 torch::Tensor attention(torch::Tensor q, torch::Tensor k, torch::Tensor v,
@@ -125,9 +149,24 @@ torch::Tensor attention(torch::Tensor q, torch::Tensor k, torch::Tensor v,
   check_bf16(q, "q");
   check_bf16(k, "k");
   check_bf16(v, "v");
-  auto o = torch::empty_like(q);
-  attention_fwd(q, k, v, o, causal, scale);
-  return o;
+  return std::get<0>(attention_fwd(q, k, v, causal, scale, false, false));
+}
+
+torch::Tensor attention_bshd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
+                             bool causal, double scale) {
+  return std::get<0>(attention_fwd(q, k, v, causal, scale, true, false));
+}
+
+std::tuple<torch::Tensor, torch::Tensor> attention_fwd_lse(
+    torch::Tensor q, torch::Tensor k, torch::Tensor v, bool causal,
+    double scale) {
+  return attention_fwd(q, k, v, causal, scale, false, true);
+}
+
+std::tuple<torch::Tensor, torch::Tensor> attention_fwd_lse_bshd(
+    torch::Tensor q, torch::Tensor k, torch::Tensor v, bool causal,
+    double scale) {
+  return attention_fwd(q, k, v, causal, scale, true, true);
 }
 
 torch::Tensor paged_decode(torch::Tensor q, torch::Tensor kc, torch::Tensor vc,
@@ -191,48 +230,6 @@ torch::Tensor paged_decode(torch::Tensor q, torch::Tensor kc, torch::Tensor vc,
   return o;
 }
 
-// Stride-aware attention: q/k/v logically [B,H,S,D] with ANY strides
-// (d contiguous); output is written [B,S,H,D]-contiguous so callers in
-// sequence-major models (UNet/Llama/Whisper blocks) skip every transpose
-// copy around the kernel.
-torch::Tensor attention_bshd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
-                             bool causal, double scale) {
-  check_bhsd(q, "q");
-  auto o = torch::empty({q.size(0), q.size(2), q.size(1), q.size(3)},
-                        q.options());
-  attention_fwd(q, k, v, o.transpose(1, 2), causal, scale);
-  return o;
-}
-
-// Training forward: the same launch, also saving the log-sum-exp that the
-// backward recomputes P from.  q/k/v may be strided (d contiguous).
-torch::Tensor new_lse(const torch::Tensor& q) {
-  check_bhsd(q, "q");
-  return torch::empty({q.size(0), q.size(1), q.size(2)},
-                      q.options().dtype(torch::kFloat32));
-}
-
-std::tuple<torch::Tensor, torch::Tensor> attention_fwd_lse(
-    torch::Tensor q, torch::Tensor k, torch::Tensor v, bool causal,
-    double scale) {
-  auto lse = new_lse(q);
-  auto o = torch::empty(q.sizes(), q.options());
-  attention_fwd(q, k, v, o, causal, scale, lse.data_ptr<float>());
-  return {o, lse};
-}
-
-// ... and its sibling with the [B,S,H,D]-contiguous output of attention_bshd
-std::tuple<torch::Tensor, torch::Tensor> attention_fwd_lse_bshd(
-    torch::Tensor q, torch::Tensor k, torch::Tensor v, bool causal,
-    double scale) {
-  auto lse = new_lse(q);
-  auto o = torch::empty({q.size(0), q.size(2), q.size(1), q.size(3)},
-                        q.options());
-  attention_fwd(q, k, v, o.transpose(1, 2), causal, scale,
-                lse.data_ptr<float>());
-  return {o, lse};
-}
-
 // Attention backward into caller-provided dq/dk/dv.  Everything is logically
 // [B,H,S,D] with any batch/head/sequence strides (d contiguous); every check
 // raises before anything is launched.
@@ -240,22 +237,13 @@ void attention_bwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
                    torch::Tensor o, torch::Tensor lse, torch::Tensor dout,
                    torch::Tensor dq, torch::Tensor dk, torch::Tensor dv,
                    bool causal, double scale) {
-  check_bhsd(q, "q");
-  check_bhsd(k, "k");
-  check_bhsd(v, "v");
+  const AttnDims d = check_qkv("attention_bwd", q, k, v);
+  const int B = d.B, Hq = d.Hq, Hkv = d.Hkv, Sq = d.Sq, Sk = d.Sk, D = d.D;
   check_bhsd(o, "o");
   check_bhsd(dout, "dout");
   check_bhsd(dq, "dq");
   check_bhsd(dk, "dk");
   check_bhsd(dv, "dv");
-  int B = q.size(0), Hq = q.size(1), Sq = q.size(2), D = q.size(3);
-  int Hkv = k.size(1), Sk = k.size(2);
-  TORCH_CHECK(D == 64 || D == 128, "attention_bwd: unsupported head_dim ", D,
-              " (supported: 64, 128)");
-  TORCH_CHECK(k.size(0) == B && k.size(3) == D && v.sizes() == k.sizes(),
-              "attention_bwd: k/v must be [B,Hkv,Sk,D] matching q's B and D");
-  TORCH_CHECK(Hkv > 0 && Hq % Hkv == 0, "GQA requires Hq % Hkv == 0, got Hq=",
-              Hq, " Hkv=", Hkv);
   TORCH_CHECK(B >= 1 && Sq >= 1 && Sk >= 1, "attention_bwd: empty input");
   TORCH_CHECK(o.sizes() == q.sizes() && dout.sizes() == q.sizes(),
               "attention_bwd: o and dout must have q's shape");
@@ -269,21 +257,13 @@ void attention_bwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
   TORCH_CHECK(!causal || Sk >= Sq, "attention_bwd: causal requires Sk >= Sq, "
               "got Sq=", Sq, " Sk=", Sk);
   auto delta = torch::empty_like(lse);
-  long long st[24] = {
-      q.stride(0), q.stride(1), q.stride(2),
-      k.stride(0), k.stride(1), k.stride(2),
-      v.stride(0), v.stride(1), v.stride(2),
-      o.stride(0), o.stride(1), o.stride(2),
-      dout.stride(0), dout.stride(1), dout.stride(2),
-      dq.stride(0), dq.stride(1), dq.stride(2),
-      dk.stride(0), dk.stride(1), dk.stride(2),
-      dv.stride(0), dv.stride(1), dv.stride(2),
-  };
+  std::vector<long long> st;
+  for (const auto& t : {q, k, v, o, dout, dq, dk, dv}) push_strides(st, t);
   int rc = fa_bwd_strided_bf16(
       q.data_ptr(), k.data_ptr(), v.data_ptr(), o.data_ptr(), dout.data_ptr(),
       lse.data_ptr<float>(), delta.data_ptr<float>(), dq.data_ptr(),
       dk.data_ptr(), dv.data_ptr(), B, Hq, Hkv, Sq, Sk, D, (float)scale,
-      causal ? 1 : 0, st, cur_stream());
+      causal ? 1 : 0, st.data(), cur_stream());
   TORCH_CHECK(rc == 0, "attention_bwd: configuration not supported by the "
               "kernel (got D=", D, " Hq=", Hq, " Hkv=", Hkv, " Sq=", Sq,
               " Sk=", Sk, " causal=", causal, ")");

@@ -111,17 +111,28 @@ class _AttentionFn(torch.autograd.Function):
         return dq, dk, dv, None, None, None, None
 
 
-def attention(q, k, v, causal: bool = False, scale: Optional[float] = None):
-    """Flash attention (K1/K5/K7). q [B,Hq,Sq,D], k/v [B,Hkv,Sk,D] bf16.
-    Differentiable on the GPU through the HIP backward."""
+def _attention(q, k, v, causal, scale, bshd: bool):
+    """The dispatch of both attention entries.  q/k/v are [B,H,S,D]-logical
+    with any strides; bshd=True returns o as [B,S,H,D] and hands the kernel
+    the strided views as they are, bshd=False returns [B,H,S,D]."""
     scale = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
     ext = _attn_train_ext(q, k, v, causal)
     if ext is not None:
-        return _AttentionFn.apply(q, k, v, causal, scale, False, ext)
+        return _AttentionFn.apply(q, k, v, causal, scale, bshd, ext)
     ext = _ext_for(q, k, v)
     if ext is None:
-        return ref.attention_ref(q, k, v, causal, scale)
-    return ext.attention(q.contiguous(), k.contiguous(), v.contiguous(), causal, scale)
+        o = ref.attention_ref(q, k, v, causal, scale)
+        return o.transpose(1, 2) if bshd else o
+    if bshd:
+        return ext.attention_bshd(q, k, v, causal, scale)
+    return ext.attention(q.contiguous(), k.contiguous(), v.contiguous(),
+                         causal, scale)
+
+
+def attention(q, k, v, causal: bool = False, scale: Optional[float] = None):
+    """Flash attention (K1/K5/K7). q [B,Hq,Sq,D], k/v [B,Hkv,Sk,D] bf16.
+    Differentiable on the GPU through the HIP backward."""
+    return _attention(q, k, v, causal, scale, False)
 
 
 def attention_qkv(q, k, v, causal: bool = False, scale: Optional[float] = None):
@@ -135,22 +146,9 @@ def attention_qkv(q, k, v, causal: bool = False, scale: Optional[float] = None):
     gradient in place.
     """
     B, S, Hq, D = q.shape
-    Sk, Hkv = k.shape[1], k.shape[2]
-    scale = scale if scale is not None else 1.0 / math.sqrt(D)
-    ext = _attn_train_ext(q.transpose(1, 2), k.transpose(1, 2),
-                          v.transpose(1, 2), causal)
-    if ext is not None:
-        o = _AttentionFn.apply(q.transpose(1, 2), k.transpose(1, 2),
-                               v.transpose(1, 2), causal, scale, True, ext)
-        return o.view(B, S, Hq * D)
-    ext = _ext_for(q, k, v)
-    if ext is None:
-        o = ref.attention_ref(q.transpose(1, 2), k.transpose(1, 2),
-                              v.transpose(1, 2), causal, scale)
-        return o.transpose(1, 2).reshape(B, S, Hq * D)
-    o = ext.attention_bshd(q.transpose(1, 2), k.transpose(1, 2),
-                           v.transpose(1, 2), causal, scale)
-    return o.view(B, S, Hq * D)
+    o = _attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2),
+                   causal, scale, True)
+    return o.reshape(B, S, Hq * D)
 
 
 def paged_decode(q, k_cache, v_cache, block_table, seq_lens, block_size: int = 0,

@@ -6,7 +6,7 @@ enforces the budgets that kept round-1 performance:
   register array silently spills and costs 3x — measured on the decode
   kernel, 3.5 -> 1.0 TB/s),
 - occupancy floors for the hot kernels (occupancy drops are how attention
-  regressions sneak in: v7 runs 3 waves/SIMD at D=64, 2 at D=128-causal).
+  regressions sneak in: the forward runs 3 waves/SIMD at D=64, 2 at D=128).
 
 Usage: python scripts/check_kernel_resources.py [file.hip ...]
 """
@@ -17,11 +17,12 @@ from pathlib import Path
 
 CSRC = Path(__file__).resolve().parent.parent / "modal_examples_amd" / "ops" / "csrc"
 
-# kernel-name substring -> minimum waves/SIMD (from the shipped v7/K6 builds)
+# kernel-name substring -> minimum waves/SIMD (from the shipped builds)
 OCCUPANCY_FLOORS = {
     "fa32_kernelILi64ELb1": 3,   # D=64 causal
     "fa32_kernelILi64ELb0": 3,   # D=64
     "fa32_kernelILi128ELb1": 2,  # D=128 causal (llama prefill)
+    "fa32_kernelILi128ELb0": 2,  # D=128
     "fa_bwd_dq_kernelILi64E": 3,     # backward dQ, D=64
     "fa_bwd_dq_kernelILi128E": 2,    # backward dQ, D=128
     "fa_bwd_dkdv_kernelILi64E": 2,   # backward dK/dV, D=64
