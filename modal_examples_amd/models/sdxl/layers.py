@@ -79,20 +79,23 @@ class Conv3x3(nn.Conv2d):
     Drop-in for nn.Conv2d(c_in, c_out, 3, padding=1): same parameters and
     state_dict.  Inference on GPU bf16 runs the MFMA kernel (with an optional
     fused residual add); training / CPU / odd dtypes use F.conv2d so autograd
-    and hermetic tests stay correct.  The [9,Kpad,C16] weight repack is cached
-    against the parameter version."""
+    and hermetic tests stay correct.  The [9,Kpad,C16] weight repack and the
+    f32 bias are cached together against the identity and version of both
+    parameters, so an in-place update of either refreshes the pair."""
 
     def __init__(self, c_in: int, c_out: int):
         super().__init__(c_in, c_out, 3, padding=1)
 
     def _packed(self):
-        w = self.weight
+        w, bias = self.weight, self.bias
+        bv = None if bias is None else bias._version
         ent = self.__dict__.get("_wr_cache")
-        if ent is None or ent[1] is not w or ent[2] != w._version:
+        if (ent is None or ent[1] is not w or ent[2] != w._version
+                or ent[3] is not bias or ent[4] != bv):
             wr = OF.repack_conv3x3_weight(w.detach())
-            b = (self.bias.detach().float().contiguous() if self.bias is not None
+            b = (bias.detach().float().contiguous() if bias is not None
                  else torch.zeros(w.shape[0], device=w.device))
-            ent = ((wr, b), w, w._version)
+            ent = ((wr, b), w, w._version, bias, bv)
             self.__dict__["_wr_cache"] = ent
         return ent[0]
 

@@ -391,30 +391,64 @@ void adamw_(torch::Tensor p, torch::Tensor g, torch::Tensor m, torch::Tensor v,
 
 // ---------------------------------------------------------------- conv (K3)
 
+void check_f32_vec(const torch::Tensor& t, const char* name, int64_t n,
+                   const char* len) {
+  TORCH_CHECK(t.is_cuda(), name, " must be on GPU");
+  TORCH_CHECK(t.scalar_type() == torch::kFloat, name, " must be fp32");
+  TORCH_CHECK(t.is_contiguous(), name, " must be contiguous");
+  TORCH_CHECK(t.numel() == n, name, " must have ", len, " = ", n,
+              " elements, got ", t.numel());
+}
+
+struct ConvDims {
+  int N, C, H, W, Ho, Wo, Kpad, C16;
+};
+
+// The argument checks of both conv entries, all on the host and before any
+// launch; `op` names the entry in the messages.  The kernel stages whole
+// 64 x 16 weight tiles and reads bias[k] and residual[o] unguarded, so a
+// short bias or a mis-packed weight has to stop here.
+ConvDims check_conv(const char* op, const torch::Tensor& x,
+                    const torch::Tensor& wr, const torch::Tensor& bias,
+                    const c10::optional<torch::Tensor>& residual, int64_t K,
+                    bool upsample) {
+  check_bf16(x, "x");
+  check_bf16(wr, "wr");
+  TORCH_CHECK(x.dim() == 4, op, ": x must be NCHW, got ", x.dim(), " dims");
+  TORCH_CHECK(wr.dim() == 3 && wr.size(0) == 9 && wr.size(1) > 0 &&
+                  wr.size(2) > 0 && wr.size(1) % 64 == 0 &&
+                  wr.size(2) % 16 == 0,
+              op, ": wr must be [9, Kpad, C16] (repacked 3x3 weights) with "
+              "Kpad % 64 == 0 and C16 % 16 == 0, got ", wr.sizes());
+  ConvDims d{(int)x.size(0), (int)x.size(1), (int)x.size(2), (int)x.size(3),
+             0, 0, (int)wr.size(1), (int)wr.size(2)};
+  d.Ho = upsample ? d.H * 2 : d.H;
+  d.Wo = upsample ? d.W * 2 : d.W;
+  TORCH_CHECK(K >= 1, op, ": K must be at least 1, got ", K);
+  TORCH_CHECK(K <= d.Kpad && d.C <= d.C16, op,
+              ": weight pack smaller than conv (K=", K, " > Kpad=", d.Kpad,
+              " or C=", d.C, " > C16=", d.C16, ")");
+  check_f32_vec(bias, "bias", K, "K");
+  if (residual.has_value()) {
+    check_bf16(*residual, "residual");
+    TORCH_CHECK(residual->dim() == 4 && residual->size(0) == d.N &&
+                    residual->size(1) == K && residual->size(2) == d.Ho &&
+                    residual->size(3) == d.Wo,
+                op, ": residual shape mismatch: ", residual->sizes(),
+                " against output [", d.N, ", ", K, ", ", d.Ho, ", ", d.Wo, "]");
+  }
+  return d;
+}
+
 torch::Tensor conv3x3(torch::Tensor x, torch::Tensor wr, torch::Tensor bias,
                       c10::optional<torch::Tensor> residual, int64_t K,
                       bool upsample) {
-  check_bf16(x, "x");
-  check_bf16(wr, "wr");
-  TORCH_CHECK(x.dim() == 4, "x must be NCHW");
-  TORCH_CHECK(wr.dim() == 3 && wr.size(0) == 9,
-              "wr must be [9, Kpad, C16] (repacked 3x3 weights)");
-  TORCH_CHECK(bias.scalar_type() == torch::kFloat && bias.is_contiguous(),
-              "bias must be fp32 contiguous");
-  int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
-  if (upsample) { H *= 2; W *= 2; }
-  int Kpad = wr.size(1), C16 = wr.size(2);
-  TORCH_CHECK(K <= Kpad && C <= C16, "weight pack smaller than conv");
-  auto out = torch::empty({N, K, H, W}, x.options());
-  const void* resp = nullptr;
-  if (residual.has_value()) {
-    check_bf16(*residual, "residual");
-    TORCH_CHECK(residual->sizes() == out.sizes(), "residual shape mismatch");
-    resp = residual->data_ptr();
-  }
-  conv3x3_bf16(x.data_ptr(), wr.data_ptr(), bias.data_ptr(), resp,
-               out.data_ptr(), nullptr, nullptr, N, C, H, W, (int)K, C16,
-               Kpad, upsample ? 1 : 0, cur_stream());
+  const ConvDims d = check_conv("conv3x3", x, wr, bias, residual, K, upsample);
+  auto out = torch::empty({d.N, K, d.Ho, d.Wo}, x.options());
+  conv3x3_bf16(x.data_ptr(), wr.data_ptr(), bias.data_ptr(),
+               residual.has_value() ? residual->data_ptr() : nullptr,
+               out.data_ptr(), nullptr, nullptr, d.N, d.C, d.Ho, d.Wo, (int)K,
+               d.C16, d.Kpad, upsample ? 1 : 0, cur_stream());
   return out;
 }
 
@@ -424,30 +458,29 @@ torch::Tensor conv3x3_gn(torch::Tensor x, torch::Tensor wr, torch::Tensor bias,
                          c10::optional<torch::Tensor> residual, int64_t K,
                          bool upsample, torch::Tensor gamma,
                          torch::Tensor beta, int64_t groups, double eps) {
-  check_bf16(x, "x");
-  check_bf16(wr, "wr");
-  int N = x.size(0), C = x.size(1), H = x.size(2), W = x.size(3);
-  long long HW = (long long)H * W;
-  int Kpad = wr.size(1), C16 = wr.size(2);
+  const ConvDims d =
+      check_conv("conv3x3_gn", x, wr, bias, residual, K, upsample);
+  check_f32_vec(gamma, "gamma", d.C, "C");
+  check_f32_vec(beta, "beta", d.C, "C");
+  TORCH_CHECK(groups >= 1 && d.C % groups == 0,
+              "conv3x3_gn: groups must be at least 1 and divide C, got groups=",
+              groups, " C=", d.C);
+  const int N = d.N, C16 = d.C16;
+  long long HW = (long long)d.H * d.W;
   auto fopt = x.options().dtype(torch::kFloat32);
   auto ws = torch::zeros({(long long)N * groups * 2}, fopt);
   auto scale = torch::empty({(long long)N * C16}, fopt);
   auto shift = torch::empty({(long long)N * C16}, fopt);
   gn_conv_coeffs_bf16(x.data_ptr(), ws.data_ptr<float>(),
                       gamma.data_ptr<float>(), beta.data_ptr<float>(),
-                      scale.data_ptr<float>(), shift.data_ptr<float>(), N, C,
+                      scale.data_ptr<float>(), shift.data_ptr<float>(), N, d.C,
                       C16, HW, (int)groups, (float)eps, cur_stream());
-  int Ho = upsample ? H * 2 : H, Wo = upsample ? W * 2 : W;
-  auto out = torch::empty({N, K, Ho, Wo}, x.options());
-  const void* resp = nullptr;
-  if (residual.has_value()) {
-    check_bf16(*residual, "residual");
-    resp = residual->data_ptr();
-  }
-  conv3x3_bf16(x.data_ptr(), wr.data_ptr(), bias.data_ptr(), resp,
+  auto out = torch::empty({N, K, d.Ho, d.Wo}, x.options());
+  conv3x3_bf16(x.data_ptr(), wr.data_ptr(), bias.data_ptr(),
+               residual.has_value() ? residual->data_ptr() : nullptr,
                out.data_ptr(), scale.data_ptr<float>(),
-               shift.data_ptr<float>(), N, C, Ho, Wo, (int)K, C16, Kpad,
-               upsample ? 1 : 0, cur_stream());
+               shift.data_ptr<float>(), N, d.C, d.Ho, d.Wo, (int)K, C16,
+               d.Kpad, upsample ? 1 : 0, cur_stream());
   return out;
 }
 

@@ -79,6 +79,42 @@ def test_conv3x3_module_cpu_fallback_matches_conv2d():
         s(x), torch.nn.functional.conv2d(x, s.weight, s.bias), atol=1e-6)
 
 
+def test_conv3x3_packed_follows_bias_and_weight_updates():
+    """The cached (repacked weight, f32 bias) pair is refreshed by an
+    in-place update of the bias alone, as it is by one of the weight."""
+    from modal_examples_amd.models.sdxl.layers import Conv3x3
+    from modal_examples_amd.ops import functional as OF
+
+    torch.manual_seed(0)
+    # bf16 is the case that matters: there the f32 bias of the pack is a
+    # copy, while for an f32 module it aliases the parameter's storage
+    for dtype in (torch.bfloat16, torch.float32):
+        m = Conv3x3(8, 16).to(dtype).eval()
+        wr0, b0 = m._packed()
+        assert b0.dtype is torch.float32
+        assert torch.equal(b0, m.bias.detach().float())
+        assert m._packed()[0] is wr0, "an unchanged module must reuse its pack"
+        old = m.bias.detach().clone()
+        with torch.no_grad():
+            m.bias.add_(1)
+        assert not torch.equal(m.bias.detach(), old)
+        assert torch.equal(m._packed()[1], (old + 1).float())
+        assert torch.equal(m._packed()[1], m.bias.detach().float())
+        with torch.no_grad():
+            m.weight.mul_(2)
+        wr2, b2 = m._packed()
+        assert torch.equal(wr2, OF.repack_conv3x3_weight(m.weight.detach()))
+        assert not torch.equal(wr2, wr0)
+        assert torch.equal(b2, m.bias.detach().float())
+        # a replaced bias parameter is a new identity at version 0
+        m.bias = torch.nn.Parameter(torch.full((16,), 3.0, dtype=dtype))
+        assert torch.equal(m._packed()[1], torch.full((16,), 3.0))
+    nb = Conv3x3(8, 16).eval()
+    nb.bias = None
+    assert torch.equal(nb._packed()[1], torch.zeros(16))
+    assert nb._packed()[0] is nb._packed()[0]
+
+
 def test_repack_conv3x3_weight_layout():
     import torch
 
