@@ -76,7 +76,8 @@ class LlamaEngine:
                  tp=None, spec_tokens: int = 0,
                  chunked_prefill: int = 0,
                  prefix_cache: bool = False,
-                 gpu_mem_util: float = 0.6):
+                 gpu_mem_util: float = 0.6,
+                 prefill_attn: str = "decode"):
         """tp: optional parallel.tp.TPGroup — head-sharded tensor parallelism
         (vllm_inference.py:180 --tensor-parallel-size role).  Every rank runs
         the same engine loop on identical requests; the KV cache holds only
@@ -93,14 +94,24 @@ class LlamaEngine:
         engine step (the --chunked-prefill-size role of deepseek_v4.py:102 /
         very_large_models.py:169) so a long prompt cannot stall decode of
         the running batch; chunks attend the cached prefix via per-row lens
-        on the paged decode kernel.
+        on the paged decode kernel, or, with prefill_attn="paged", in one
+        call of the MFMA paged prefill kernel per layer.
 
         prefix_cache=True: block-level KV prefix caching (the RadixAttention
         /unified-radix-tree role of inkling_small.py:99 and vLLM's automatic
         prefix caching) — FULL prompt blocks are chain-hashed; a request
         whose prompt prefix matches cached blocks shares them (refcounted,
         never written) and prefills only the suffix.  Shared system prompts
-        cost their KV compute once.
+        cost their KV compute once.  The suffix attends the shared blocks
+        through the same lane as a prefill chunk, so prefill_attn selects
+        its kernel too.
+
+        prefill_attn: the attention kernel of those two lanes.  "decode"
+        (default) turns a chunk of C tokens into C rows of the paged decode
+        kernel, each sweeping the whole prefix; "paged" calls
+        ops.paged_prefill once per layer on the request's one block-table
+        row (csrc/attention_prefill_paged.hip).  Monolithic prefill,
+        decode and speculative verification are the same under both.
 
         gpu_mem_util: fraction of free HBM the KV pool claims when
         kv_blocks is unset (--gpu-memory-utilization / --mem-fraction-static
@@ -111,6 +122,10 @@ class LlamaEngine:
         self.spec_proposed = 0   # drafts offered
         self.spec_accepted = 0   # drafts accepted (emitted without a step)
         self.chunked_prefill = chunked_prefill
+        if prefill_attn not in ("decode", "paged"):
+            raise ValueError(f"prefill_attn must be 'decode' or 'paged', got "
+                             f"{prefill_attn!r}")
+        self.prefill_attn = prefill_attn
         self.prefilling: List[Request] = []  # long prompts mid-chunk
         self.prefix_cache = prefix_cache
         self._pc_map: Dict = {}    # chain-hash -> block id
@@ -627,7 +642,9 @@ class LlamaEngine:
 
         Rows pos..pos+C-1 share r's block table with per-row lens, so the
         paged decode kernel gives each chunk token exactly-causal attention
-        over the cached prefix + earlier in-chunk tokens.  bt_d/active_d
+        over the cached prefix + earlier in-chunk tokens; under
+        prefill_attn="paged" the same attention is one paged_prefill call
+        on the one table row.  bt_d/active_d
         stay zero until completion so graph-mode decode keeps treating the
         slot as inactive (its pad writes go to block 0)."""
         dev = self.device
@@ -641,9 +658,6 @@ class LlamaEngine:
                              device=dev)
         bt_row[: len(r.blocks)] = torch.tensor(r.blocks, dtype=torch.int32,
                                                device=dev)
-        # materialized (not expand()ed): the HIP kernel reads bt row-strided
-        bt = bt_row.unsqueeze(0).repeat(end - start, 1)
-        lens = pos + 1
         blks = bt_row[(pos // BLOCK).long()].long()
         offs = (pos % BLOCK).long()
 
@@ -651,9 +665,28 @@ class LlamaEngine:
             self.cache_k[li][blks, :, offs] = k[:, 0].to(self.cache_k.dtype)
             self.cache_v[li][blks, :, offs] = v[:, 0].to(self.cache_v.dtype)
 
-        def kv_attend(li, q):
-            return OF.paged_decode(q, self.cache_k[li], self.cache_v[li],
-                                   bt, lens, BLOCK)
+        if self.prefill_attn == "paged":
+            # the chunk as ONE ragged sequence of end-start new tokens over
+            # the request's real table row; decode_step appends a layer's
+            # K/V before it attends, so the cache holds them as the op expects
+            bt = bt_row.unsqueeze(0)
+            cu_q = torch.tensor([0, end - start], dtype=torch.int32,
+                                device=dev)
+            seq_len = torch.tensor([end], dtype=torch.int32, device=dev)
+
+            def kv_attend(li, q):
+                return OF.paged_prefill(q, self.cache_k[li], self.cache_v[li],
+                                        bt, cu_q, seq_len, BLOCK,
+                                        max_q_len=end - start)
+        else:
+            # materialized (not expand()ed): the HIP kernel reads bt
+            # row-strided
+            bt = bt_row.unsqueeze(0).repeat(end - start, 1)
+            lens = pos + 1
+
+            def kv_attend(li, q):
+                return OF.paged_decode(q, self.cache_k[li], self.cache_v[li],
+                                       bt, lens, BLOCK)
 
         logits = self.model.decode_step(toks, pos, kv_append, kv_attend)
         r.pf_done = end

@@ -23,6 +23,7 @@ HIP_SOURCES = [
     "attention_fwd32.hip",
     "attention_bwd.hip",
     "attention_decode.hip",
+    "attention_prefill_paged.hip",
     "norms.hip",
     "elementwise.hip",
     "adamw.hip",

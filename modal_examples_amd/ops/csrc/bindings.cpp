@@ -26,6 +26,9 @@ int fa_bwd_strided_bf16(const void*, const void*, const void*, const void*,
 int paged_decode_bf16(const void*, const void*, const void*, const int*,
                       const int*, void*, float*, int, int, int, int, int,
                       int, int, float, int, hipStream_t);
+int paged_prefill_bf16(const void*, const void*, const void*, const int*,
+                       const int*, const int*, void*, int, int, int, int, int,
+                       int, int, float, int, hipStream_t);
 void groupnorm_silu_bf16(const void*, void*, float*, const float*,
                          const float*, int, int, long long, int, float, int,
                          hipStream_t);
@@ -227,6 +230,72 @@ torch::Tensor paged_decode(torch::Tensor q, torch::Tensor kc, torch::Tensor vc,
   TORCH_CHECK(rc == 0, "paged_decode: configuration not supported by the "
               "kernel (head_dim must be 64 or 128, Hq a multiple of Hkv and "
               "Hq/Hkv in 1..8; got D=", D, " Hq=", Hq, " Hkv=", Hkv, ")");
+  return o;
+}
+
+// Causal attention of a ragged batch of new query tokens q [T,Hq,D] (rows
+// cu_q[b]..cu_q[b+1] belong to sequence b) against a paged cache that already
+// holds their K/V; seq_lens[b] counts the new tokens too.  Every check raises
+// before anything is launched.  What only the device knows stays a
+// precondition (csrc/attention_prefill_paged.hip): seq_lens[b] >= the
+// sequence's query count, valid table entries below seq_lens[b], and
+// max_q_len >= the longest query run.
+torch::Tensor paged_prefill(torch::Tensor q, torch::Tensor kc, torch::Tensor vc,
+                            torch::Tensor block_table, torch::Tensor cu_q,
+                            torch::Tensor seq_lens, int64_t block_size,
+                            double scale, int64_t max_q_len) {
+  check_bf16(q, "q");
+  TORCH_CHECK(q.dim() == 3, "paged_prefill: q must be [T,Hq,D]");
+  const bool kv_fp8 = kc.scalar_type() == torch::kFloat8_e4m3fn;
+  TORCH_CHECK(kv_fp8 || kc.scalar_type() == torch::kBFloat16,
+              "k_cache must be bf16 or float8_e4m3fn");
+  TORCH_CHECK(vc.scalar_type() == kc.scalar_type(), "kv cache dtype mismatch");
+  TORCH_CHECK(kc.dim() == 4 && vc.sizes() == kc.sizes() &&
+                  kc.is_contiguous() && vc.is_contiguous(),
+              "paged_prefill: k_cache/v_cache must be contiguous "
+              "[blocks,Hkv,block_size,D] of one shape");
+  const int64_t T = q.size(0);
+  const int Hq = q.size(1), D = q.size(2), Hkv = kc.size(1);
+  TORCH_CHECK(D == 64 || D == 128, "paged_prefill: unsupported head_dim ", D,
+              " (supported: 64, 128)");
+  TORCH_CHECK(kc.size(3) == D, "paged_prefill: k_cache head_dim ", kc.size(3),
+              " != q head_dim ", D);
+  TORCH_CHECK(Hkv > 0 && Hq % Hkv == 0, "GQA requires Hq % Hkv == 0, got Hq=",
+              Hq, " Hkv=", Hkv);
+  TORCH_CHECK(block_size > 0 && kc.size(2) == block_size,
+              "paged_prefill: block_size must be positive and the cache's "
+              "third dim, got block_size=", block_size, " cache ", kc.sizes());
+  TORCH_CHECK(seq_lens.scalar_type() == torch::kInt32 && seq_lens.dim() == 1 &&
+                  seq_lens.is_contiguous(),
+              "paged_prefill: seq_lens must be int32 [B] contiguous");
+  const int64_t B = seq_lens.size(0);
+  TORCH_CHECK(block_table.scalar_type() == torch::kInt32 &&
+                  block_table.dim() == 2 && block_table.size(0) == B &&
+                  block_table.is_contiguous(),
+              "paged_prefill: block_table must be int32 [B=", B,
+              ", max_blocks] contiguous, got ", block_table.sizes());
+  TORCH_CHECK(cu_q.scalar_type() == torch::kInt32 && cu_q.dim() == 1 &&
+                  cu_q.size(0) == B + 1 && cu_q.is_contiguous(),
+              "paged_prefill: cu_q must be int32 [B+1=", B + 1, "], got ",
+              cu_q.sizes());
+  for (const torch::Tensor* t : {&kc, &vc, &block_table, &cu_q, &seq_lens})
+    TORCH_CHECK(t->device() == q.device(),
+                "paged_prefill: all tensors must be on q's device");
+  auto o = torch::empty_like(q);
+  if (T == 0) return o;  // nothing to attend: max_q_len=None arrives as T = 0
+  TORCH_CHECK(max_q_len >= 1, "paged_prefill: max_q_len must be at least 1, "
+              "got ", max_q_len);
+  TORCH_CHECK(B >= 1, "paged_prefill: ", T, " query rows but no sequence");
+  max_q_len = std::min<int64_t>(max_q_len, T);  // no run is longer than T
+  int rc = paged_prefill_bf16(
+      q.data_ptr(), kc.data_ptr(), vc.data_ptr(), block_table.data_ptr<int>(),
+      cu_q.data_ptr<int>(), seq_lens.data_ptr<int>(), o.data_ptr(), (int)B, Hq,
+      Hkv, D, (int)block_size, (int)block_table.size(1), (int)max_q_len,
+      (float)scale, kv_fp8 ? 1 : 0, cur_stream());
+  TORCH_CHECK(rc == 0, "paged_prefill: configuration not supported by the "
+              "kernel (head_dim must be 64 or 128, Hq a multiple of Hkv, B "
+              "and Hq at most 65535; got D=", D, " Hq=", Hq, " Hkv=", Hkv,
+              " B=", B, ")");
   return o;
 }
 
@@ -663,6 +732,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attention_bwd", &attention_bwd,
         "flash attention bwd bf16 into caller-provided dq/dk/dv");
   m.def("paged_decode", &paged_decode, "paged KV decode attention (K6)");
+  m.def("paged_prefill", &paged_prefill,
+        "paged KV prefill attention: ragged causal chunks over a cached "
+        "prefix (K6)");
   m.def("groupnorm_silu", &groupnorm_silu);
   m.def("layernorm", &layernorm);
   m.def("rmsnorm", &rmsnorm);

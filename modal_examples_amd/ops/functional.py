@@ -171,6 +171,40 @@ def paged_decode(q, k_cache, v_cache, block_table, seq_lens, block_size: int = 0
                             seq_lens.int(), block_size, scale)
 
 
+def paged_prefill(q, k_cache, v_cache, block_table, cu_q, seq_lens,
+                  block_size: int, scale: Optional[float] = None,
+                  max_q_len: Optional[int] = None):
+    """Prefill attention over a paged KV cache (K6): causal attention of a
+    ragged batch of NEW tokens against a cache that already holds their K/V
+    — chunked prefill and the suffix after a prefix-cache hit.
+
+    q [T,Hq,D]: rows cu_q[b]..cu_q[b+1] are sequence b's new tokens (cu_q
+    int32 [B+1]); caches [blocks,Hkv,block_size,D], bf16 or float8_e4m3fn;
+    block_table int32 [B,max_blocks]; seq_lens int32 [B], the cached length
+    INCLUDING the new tokens, so query i of n_b sits at position
+    seq_lens[b] - n_b + i.  max_q_len is a host-side bound on the longest
+    run of new tokens (it sizes the grid, nothing is read back); None means
+    T, which is always safe.  Returns [T,Hq,D]."""
+    if block_table is None:
+        raise ValueError("paged_prefill needs a block_table (there is no "
+                         "contiguous-cache mode)")
+    scale = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
+    ext = _ext_for(q)
+    if ext is None:
+        if k_cache.dtype not in (torch.float32, torch.float64, torch.bfloat16,
+                                 torch.float16):
+            k_cache = k_cache.to(torch.float32)
+            v_cache = v_cache.to(torch.float32)
+        return ref.paged_prefill_ref(q, k_cache, v_cache, block_table, cu_q,
+                                     seq_lens, block_size, scale)
+    # .contiguous() also materializes expand()ed (stride-0) block tables —
+    # the kernel indexes bt + row*stride and would read out of bounds.
+    return ext.paged_prefill(q.contiguous(), k_cache, v_cache,
+                             block_table.contiguous(), cu_q.int().contiguous(),
+                             seq_lens.int().contiguous(), block_size, scale,
+                             q.shape[0] if max_q_len is None else max_q_len)
+
+
 def groupnorm_silu(x, gamma, beta, groups: int = 32, eps: float = 1e-5,
                    do_silu: bool = True):
     ext = _ext_for(x, gamma, beta)

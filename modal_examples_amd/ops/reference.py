@@ -132,6 +132,43 @@ def paged_decode_ref(q, k_cache, v_cache, block_table, seq_lens, block_size,
     return out
 
 
+def paged_prefill_ref(q, k_cache, v_cache, block_table, cu_q, seq_lens,
+                      block_size, scale: Optional[float] = None):
+    """Causal attention of a ragged batch of NEW tokens over a paged cache
+    that already holds their K/V — the specification of
+    csrc/attention_prefill_paged.hip.
+
+    q [T,Hq,D]: rows cu_q[b]..cu_q[b+1] (n_b of them) are sequence b's new
+    tokens.  Cache [nblocks,Hkv,block_size,D], block_table [B,max_blocks],
+    seq_lens[b] = S_b the cached length INCLUDING the new tokens: query i of
+    sequence b sits at position S_b - n_b + i and sees kv positions <= that.
+    Rows at a negative position (S_b < n_b) see nothing and return zeros.
+    Works in fp32, or fp64 for fp64 inputs; returns q's dtype."""
+    T, Hq, D = q.shape
+    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    Hkv = k_cache.shape[1]
+    G = Hq // Hkv
+    out = torch.zeros_like(q)
+    for b in range(seq_lens.shape[0]):
+        lo, hi, S = int(cu_q[b]), int(cu_q[b + 1]), int(seq_lens[b])
+        n = hi - lo
+        if n == 0 or S <= 0:
+            continue
+        blks = block_table[b, :(S + block_size - 1) // block_size].long()
+        # [Hkv, S, D]: the sequence's rows gathered through its table
+        kb = _wide(k_cache[blks]).transpose(0, 1).reshape(Hkv, -1, D)[:, :S]
+        vb = _wide(v_cache[blks]).transpose(0, 1).reshape(Hkv, -1, D)[:, :S]
+        qb = _wide(q[lo:hi]).transpose(0, 1).reshape(Hkv, G, n, D)
+        s = torch.matmul(qb, kb.unsqueeze(1).transpose(-1, -2)) * scale
+        pos = torch.arange(S - n, S, device=q.device)  # position of query i
+        seen = torch.arange(S, device=q.device)[None, :] <= pos[:, None]
+        p = torch.softmax(s.masked_fill(~seen, float("-inf")), dim=-1)
+        p = p.masked_fill(~seen, 0.0)  # also clears the NaN of all-masked rows
+        o = torch.matmul(p, vb.unsqueeze(1)).reshape(Hq, n, D)
+        out[lo:hi] = o.transpose(0, 1).to(q.dtype)
+    return out
+
+
 def groupnorm_silu_ref(x, gamma, beta, groups, eps=1e-5, do_silu=True):
     y = torch.nn.functional.group_norm(
         x.float(), groups, gamma.float(), beta.float(), eps

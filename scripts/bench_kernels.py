@@ -113,6 +113,89 @@ def bench_decode(results):
             "pct_hbm": round(100 * gb / dt / HBM_CEIL_GBS, 1)}
 
 
+def _alternate(fns, window_s=0.25, rounds=3):
+    """Best per-call time of each fn, timed in alternating windows of about
+    window_s (at least 3 calls) after a warm-up of every fn."""
+    iters = []
+    for fn in fns:
+        fn()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        iters.append(max(3, int(window_s / (time.perf_counter() - t0))))
+    best = [float("inf")] * len(fns)
+    for _ in range(rounds):
+        for i, fn in enumerate(fns):
+            best[i] = min(best[i], timeit(fn, iters=iters[i], warmup=1))
+    return best
+
+
+def bench_paged_prefill(results):
+    """A chunk of C new tokens over a cached prefix of P (Llama-3-8B heads,
+    block 16, shuffled table): F.paged_prefill against the lane it replaces,
+    F.paged_decode over C rows with the table repeated and lens = P+1..P+C.
+    Both are timed in one process, alternating; FLOPs = 4*Hq*D*sum_i(P+i+1).
+    The outputs are compared at every timed shape (each kernel is held to
+    2e-2/2e-2 of the truth by the tests, so to twice that of each other).
+    At P = 0 the dense causal F.attention at S = C is the upper yardstick."""
+    Hq, Hkv, D, bs = 32, 8, 128, 16
+    g = torch.Generator(device="cuda").manual_seed(0)
+
+    def randn(*shape):
+        return torch.randn(*shape, device="cuda", generator=g)
+
+    for fp8 in (False, True):
+        cdt = torch.float8_e4m3fn if fp8 else torch.bfloat16
+        amp = 0.5 if fp8 else 1.0
+        for C in (128, 512, 2048):
+            for P in (0, 2048, 8192, 32768):
+                S = P + C
+                nblk = S // bs
+                kc = (randn(nblk, Hkv, bs, D) * amp).to(cdt)
+                vc = (randn(nblk, Hkv, bs, D) * amp).to(cdt)
+                q = randn(C, Hq, D).to(torch.bfloat16)
+                row = torch.randperm(nblk, device="cuda", generator=g).int()
+                bt1 = row.unsqueeze(0)
+                cu = torch.tensor([0, C], dtype=torch.int32, device="cuda")
+                sl = torch.tensor([S], dtype=torch.int32, device="cuda")
+                btc = row.unsqueeze(0).repeat(C, 1)
+                lens = torch.arange(P + 1, S + 1, dtype=torch.int32,
+                                    device="cuda")
+
+                def new():
+                    return F.paged_prefill(q, kc, vc, bt1, cu, sl, bs,
+                                           max_q_len=C)
+
+                def old():
+                    return F.paged_decode(q, kc, vc, btc, lens, bs)
+
+                a, b = new().float(), old().float()
+                diff = (a - b).abs()
+                agree = bool((diff <= 4e-2 + 4e-2 * b.abs()).all())
+                fns = [new, old]
+                if P == 0 and not fp8:
+                    qd = q.transpose(0, 1).unsqueeze(0).contiguous()
+                    kd = randn(1, Hkv, C, D).to(torch.bfloat16)
+                    vd = randn(1, Hkv, C, D).to(torch.bfloat16)
+                    fns.append(lambda: F.attention(qd, kd, vd, causal=True))
+                ts = _alternate(fns)
+                flops = 4.0 * Hq * D * (C * P + C * (C + 1) / 2)
+                r = {"paged_ms": round(ts[0] * 1e3, 4),
+                     "paged_TF": round(flops / ts[0] / 1e12, 1),
+                     "decode_lane_ms": round(ts[1] * 1e3, 4),
+                     "decode_lane_TF": round(flops / ts[1] / 1e12, 1),
+                     "speedup": round(ts[1] / ts[0], 2),
+                     "max_abs_diff": round(float(diff.max()), 5),
+                     "outputs_agree": agree}
+                if len(ts) == 3:
+                    r["dense_causal_ms"] = round(ts[2] * 1e3, 4)
+                    r["dense_causal_TF"] = round(flops / ts[2] / 1e12, 1)
+                name = f"paged_prefill/{'fp8' if fp8 else 'bf16'}_c{C}_p{P}"
+                results[name] = r
+                print(name, json.dumps(r), flush=True)
+
+
 def bench_memory_ops(results):
     x = torch.randn(16, 1280, 64, 64, device="cuda", dtype=torch.bfloat16)
     g = torch.randn(1280, device="cuda")
@@ -173,12 +256,14 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--only", default="",
                     help="comma-separated groups: attention, attention_bwd, "
-                         "decode, memory_ops, gemm_reference (default: all)")
+                         "decode, paged_prefill, memory_ops, gemm_reference "
+                         "(default: all)")
     args = ap.parse_args()
     assert torch.cuda.is_available()
     groups = {"attention": bench_attention,
               "attention_bwd": bench_attention_bwd,
-              "decode": bench_decode, "memory_ops": bench_memory_ops,
+              "decode": bench_decode, "paged_prefill": bench_paged_prefill,
+              "memory_ops": bench_memory_ops,
               "gemm_reference": bench_gemm_reference}
     only = [g for g in args.only.split(",") if g] or list(groups)
     results = {}

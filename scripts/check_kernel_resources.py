@@ -28,6 +28,8 @@ OCCUPANCY_FLOORS = {
     "fa_bwd_dkdv_kernelILi64E": 2,   # backward dK/dV, D=64
     "fa_bwd_dkdv_kernelILi128E": 1,  # dK^T+dV^T accumulators take 128 AGPRs
     "fa_bwd_delta_kernel": 8,
+    "paged_prefill_kernelILi64E": 3,   # bf16 and fp8 cache, the forward's 3
+    "paged_prefill_kernelILi128E": 2,  # bf16 and fp8 cache, the forward's 2
     "decode_kernel": 2,
     "decode_merge_kernel": 4,
 }
