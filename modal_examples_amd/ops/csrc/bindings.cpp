@@ -497,6 +497,14 @@ ConvDims check_conv(const char* op, const torch::Tensor& x,
   TORCH_CHECK(K <= d.Kpad && d.C <= d.C16, op,
               ": weight pack smaller than conv (K=", K, " > Kpad=", d.Kpad,
               " or C=", d.C, " > C16=", d.C16, ")");
+  // The kernel addresses one input image, one 64-plane output slab and the
+  // packed weights with 32-bit byte offsets.
+  TORCH_CHECK((int64_t)d.C16 * d.H * d.W < (1ll << 30) &&
+                  64ll * d.Ho * d.Wo < (1ll << 31) &&
+                  9ll * d.Kpad * d.C16 < (1ll << 31),
+              op, ": too large for the kernel's 32-bit offsets (C16*H*W must "
+              "stay below 2^30, 64*Ho*Wo and 9*Kpad*C16 below 2^31), got x ",
+              x.sizes(), " wr ", wr.sizes());
   check_f32_vec(bias, "bias", K, "K");
   if (residual.has_value()) {
     check_bf16(*residual, "residual");

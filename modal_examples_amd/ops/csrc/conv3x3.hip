@@ -22,7 +22,23 @@
 //    run of pixel tiles (bijective chunk swizzle, guide §5 T1/m204).
 //  - Wave w owns output rows {2w, 2w+1} and BOTH 32-k fragments: 36 MFMA per
 //    18 ds_read_b128 per chunk (2:1, the m97 GEMM ratio).
+//  - Staging is software-pipelined: chunk cc+1's input and weight loads
+//    issue back to back right after chunk cc's second barrier and are first
+//    waited for after chunk cc's last MFMA.  Every input load is
+//    UNCONDITIONAL from a clamped, always-valid address (row/col clamped into
+//    the image, channel clamped to C-1, slot clamped to the last one); the
+//    zero fill for padding pixels, spare slots and channels past C is an AND
+//    with a 0/-1 mask when the values are packed for the LDS write.  A
+//    `cond ? load : 0` per element makes hipcc branch around each load and
+//    wait vmcnt(0) per element (guide §5 trap 4(c)), which serialised the
+//    whole chunk in front of its MFMAs.
 //  - Epilogue fuses bias add and an optional residual add (VAEResnet skip).
+//    The block's 64 bias values sit in LDS from the prologue; residual loads
+//    are unconditional (clamped on edge tiles) and issue 16 at a time with
+//    one wait per batch; interior tiles carry no per-element condition, edge
+//    tiles mask only the stores.
+//  - Offsets inside one image are 32-bit: the host checks C16*Hs*Ws and
+//    64*H*W below 2^31 elements (bindings.cpp check_conv).
 //
 // The kernel is stride-1/pad-1 only; stride-2 downsample convs (3 per UNet
 // fwd) stay on the library path.
@@ -30,6 +46,7 @@
 
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 
 #define CV_NW 4      // waves per block
 #define CV_COLS 32   // output cols per block
@@ -38,8 +55,25 @@
 
 typedef __attribute__((ext_vector_type(16))) float f32x16c;
 
+// GN staging value: silu(x*scale+shift) of one bf16, back to bf16 bits.
+DEV_INLINE unsigned gn_silu_bf16(unsigned raw, float sc, float sh) {
+  float f = bf2f((short)raw) * sc + sh;
+  f = f / (1.f + __expf(-f));
+  return (unsigned)(unsigned short)f2bf(f);
+}
+
+// A wave-uniform value moved to an SGPR.  The builtin readfirstlane is folded
+// away when the compiler can prove the value uniform - and then leaves it in
+// a VGPR; the s_nop covers the VALU-write -> readfirstlane hazard.
+DEV_INLINE int to_sgpr(int v) {
+  int s;
+  asm volatile("s_nop 0\n\tv_readfirstlane_b32 %0, %1" : "=s"(s) : "v"(v));
+  return s;
+}
+
 // RPW = output rows per wave (block rows = CV_NW*RPW).  RPW=2 runs 3
-// waves/SIMD; RPW=4 doubles MFMA per staged byte/A-read at 2 waves/SIMD.
+// waves/SIMD (its register budget: __launch_bounds__ below); RPW=4 doubles
+// MFMA per staged byte/A-read at 1 wave/SIMD (128 accumulator registers).
 // LDS patch: [rows+2][CV_COLS+2][CV_CC] bf16, c innermost.
 #define PATCH_C (CV_COLS + 2)
 
@@ -58,7 +92,8 @@ typedef __attribute__((ext_vector_type(16))) float f32x16c;
 // with per-(n,c) coefficients from gn_conv_coeffs_bf16 (norms.hip).  The
 // gn_norm write+read pass over the full tensor disappears.
 template <bool UP, bool GN, int RPW>
-__global__ __launch_bounds__(CV_NW * WAVE) void conv3x3_kernel(
+__global__ __launch_bounds__(CV_NW * WAVE, RPW == 2 ? 3 : 1)
+void conv3x3_kernel(
     const short* __restrict__ in, const short* __restrict__ wr,
     const float* __restrict__ bias, const short* __restrict__ res,
     short* __restrict__ out, const float* __restrict__ gn_scale,
@@ -72,6 +107,7 @@ __global__ __launch_bounds__(CV_NW * WAVE) void conv3x3_kernel(
       (STAGE_SLOTS + CV_NW * WAVE - 1) / (CV_NW * WAVE);
   __shared__ alignas(16) short patch[PATCH_ELEMS];
   __shared__ alignas(16) short wlds[WLDS_ELEMS];
+  __shared__ alignas(16) float bias_s[CV_BK];
 
   const int tid = threadIdx.x;
   const int w = tid / WAVE;
@@ -89,99 +125,152 @@ __global__ __launch_bounds__(CV_NW * WAVE) void conv3x3_kernel(
     int xcd = bid & 7, pos = bid >> 3;
     bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + pos;
   }
-  const int ktile = bid / npix;
+  // the division runs on the VALU and its (block-uniform) result would stay
+  // in VGPRs, with every tile coordinate and address base built on it
+  const int ktile = to_sgpr(bid / npix);
   const int pix = bid - ktile * npix;
-  const int y0 = (pix / npix_x) * CV_ROWS;
-  const int x0 = (pix - (pix / npix_x) * npix_x) * CV_COLS;
+  const int pix_y = pix / npix_x;
+  const int y0 = pix_y * CV_ROWS;
+  const int x0 = (pix - pix_y * npix_x) * CV_COLS;
   const int k0 = ktile * CV_BK;
 
   const long long in_n = (long long)n * C * Hs * Ws;
   const int nc = C16 / CV_CC;
 
+  // bias: the block's 64 values go to LDS once (index clamped to K-1; the
+  // loop's first barrier orders this write before the epilogue's reads).
+  if (tid < CV_BK) bias_s[tid] = bias[min(k0 + tid, K - 1)];
+
   // ---- staging: slot s = (row, col, c-oct); thread gathers 8 strided
   // channel values (coalesced across lanes: consecutive threads read
   // consecutive x) and writes ONE bf16x8 to the c-contiguous LDS slot.
-  bf16x8 sreg[SLOTS_PER_T];
+  // Fixed per slot for the whole kernel: the byte offset inside image n of
+  // (clamped pixel, next chunk's channel oct*8) - advanced by 16 channels per
+  // stage_load -, the pixel's last valid offset (channel C-1), the LDS
+  // element offset, and a 0/-1 mask that is 0 for padding pixels and for the
+  // slots past STAGE_SLOTS.
+  const char* in_img = (const char*)(in + in_n);
+  const unsigned hwb = (unsigned)Hs * (unsigned)Ws * 2u;  // channel stride, B
+  unsigned soff[SLOTS_PER_T], soff_max[SLOTS_PER_T];
+  int slds[SLOTS_PER_T], smask[SLOTS_PER_T];
+#pragma unroll
+  for (int i = 0; i < SLOTS_PER_T; ++i) {
+    const int s_raw = i * CV_NW * WAVE + tid;
+    const int s = min(s_raw, STAGE_SLOTS - 1);
+    const int col = s % PATCH_C;
+    const int u = s / PATCH_C;
+    const int oct = u & 1;
+    const int row = u >> 1;
+    const int y = y0 + row - 1;
+    const int x = x0 + col - 1;
+    const bool live =
+        s_raw < STAGE_SLOTS && y >= 0 && y < H && x >= 0 && x < W;
+    const int yc = min(max(y, 0), H - 1);
+    const int xc = min(max(x, 0), W - 1);
+    const unsigned sy = UP ? (yc >> 1) : yc;
+    const unsigned sx = UP ? (xc >> 1) : xc;
+    const unsigned pix = (sy * (unsigned)Ws + sx) * 2u;
+    soff[i] = pix + (unsigned)(oct * 8) * hwb;
+    soff_max[i] = pix + (unsigned)(C - 1) * hwb;
+    slds[i] = (row * PATCH_C + col) * CV_CC + oct * 8;
+    // opaque to the optimiser: as a visible `live ? v : 0` the zero fill
+    // turns back into a branch around every load
+    int m = live ? -1 : 0;
+    asm volatile("" : "+v"(m));
+    smask[i] = m;
+  }
+
+  // All of a chunk's loads are unconditional and independent, so they issue
+  // back to back; nothing here consumes a loaded value.
+  unsigned sraw[SLOTS_PER_T][8];
+  float gsc[GN ? CV_CC : 1], gsh[GN ? CV_CC : 1];  // chunk's GN coeffs
   auto stage_load = [&](int cc) {
-    const int c0 = cc * CV_CC;
 #pragma unroll
     for (int i = 0; i < SLOTS_PER_T; ++i) {
-      int s = i * CV_NW * WAVE + tid;
-      bf16x8 v = {0, 0, 0, 0, 0, 0, 0, 0};
-      if (s < STAGE_SLOTS) {
-        int col = s % PATCH_C;
-        int u = s / PATCH_C;
-        int oct = u & 1;
-        int row = u >> 1;
-        int y = y0 + row - 1;
-        int x = x0 + col - 1;
-        if (y >= 0 && y < H && x >= 0 && x < W) {
-          const int sy = UP ? (y >> 1) : y;
-          const int sx = UP ? (x >> 1) : x;
-          const long long hw = (long long)Hs * Ws;
-          const short* src = in + in_n + (long long)(c0 + oct * 8) * hw +
-                             (long long)sy * Ws + sx;
-          // GN coeffs: tiny [N, C16] arrays, L1/L2-broadcast across pixels
-          const float* gsc = GN ? gn_scale + (long long)n * C16 + c0 + oct * 8
-                                : nullptr;
-          const float* gsh = GN ? gn_shift + (long long)n * C16 + c0 + oct * 8
-                                : nullptr;
 #pragma unroll
-          for (int j = 0; j < 8; ++j) {
-            // keep the load as a SELECT (not a branch): branchy loads
-            // serialize behind exec-mask updates and exposed the staging
-            // latency (measured 13.3 -> 9.8 img/s whole-step)
-            int c = c0 + oct * 8 + j;
-            short raw = (c < C) ? src[(long long)j * hw] : (short)0;
-            if (GN) {
-              float f = bf2f(raw) * gsc[j] + gsh[j];
-              f = f / (1.f + __expf(-f));
-              raw = (c < C) ? f2bf(f) : (short)0;
-            }
-            v[j] = raw;
-          }
-        }
+      for (int j = 0; j < 8; ++j) {
+        const unsigned o = min(soff[i] + (unsigned)j * hwb, soff_max[i]);
+        sraw[i][j] = *(const unsigned short*)(in_img + o);
       }
-      sreg[i] = v;
+      soff[i] += CV_CC * hwb;
+    }
+    if constexpr (GN) {
+      // tiny [N, C16] arrays at a block-uniform address
+      const float* ps = gn_scale + (long long)n * C16 + cc * CV_CC;
+      const float* ph = gn_shift + (long long)n * C16 + cc * CV_CC;
+#pragma unroll
+      for (int j = 0; j < CV_CC; ++j) {
+        gsc[j] = ps[j];
+        gsh[j] = ph[j];
+      }
     }
   };
-  auto stage_write = [&]() {
+  // The first use of the loaded values: (GN: normalise + SiLU,) pack pairs,
+  // AND with the slot mask and the channel-tail mask, one 16-byte LDS write.
+  auto stage_write = [&](int cc) {
+    const int nv = C - cc * CV_CC;  // channels of this chunk below C (uniform)
 #pragma unroll
     for (int i = 0; i < SLOTS_PER_T; ++i) {
-      int s = i * CV_NW * WAVE + tid;
-      if (s < STAGE_SLOTS) {
-        int col = s % PATCH_C;
-        int u = s / PATCH_C;
-        int oct = u & 1;
-        int row = u >> 1;
-        *(bf16x8*)&patch[(row * PATCH_C + col) * CV_CC + oct * 8] = sreg[i];
+      const int o8 = slds[i] & 8;  // oct * 8
+      i32x4 pk;
+#pragma unroll
+      for (int d = 0; d < 4; ++d) {
+        unsigned lo = sraw[i][2 * d], hi = sraw[i][2 * d + 1];
+        // pin the first use here: left alone, hipcc hoists the pair packing
+        // (and with it the wait for these loads) above the MFMA block
+        asm volatile("" : "+v"(lo), "+v"(hi));
+        if constexpr (GN) {
+          lo = gn_silu_bf16(lo, o8 ? gsc[8 + 2 * d] : gsc[2 * d],
+                            o8 ? gsh[8 + 2 * d] : gsh[2 * d]);
+          hi = gn_silu_bf16(hi, o8 ? gsc[9 + 2 * d] : gsc[1 + 2 * d],
+                            o8 ? gsh[9 + 2 * d] : gsh[1 + 2 * d]);
+        }
+        pk[d] = (int)((lo | (hi << 16)) & (unsigned)smask[i]);
       }
+      // channel tail, last chunk only: a block-uniform branch round pure
+      // ALU work; the masks are sign-bit arithmetic, never a select
+      if (nv < CV_CC) {
+        const int nvl = nv - o8;  // this oct's channels below C
+#pragma unroll
+        for (int d = 0; d < 4; ++d) {
+          const unsigned lo = (unsigned)((2 * d - nvl) >> 31);
+          const unsigned hi = (unsigned)((2 * d + 1 - nvl) >> 31);
+          pk[d] &= (int)((lo & 0xffffu) | (hi & 0xffff0000u));
+        }
+      }
+      // only the last round has spare slots
+      if ((i + 1) * CV_NW * WAVE <= STAGE_SLOTS ||
+          i * CV_NW * WAVE + tid < STAGE_SLOTS)
+        *(i32x4*)&patch[slds[i]] = pk;
     }
   };
 
-  // weight staging: slot = (tap, k-row, c-oct); one bf16x8 each.
+  // weight staging: slot = (tap, k-row, c-oct); one bf16x8 each.  The spare
+  // slots of the last round re-read the last slot (no branch round a load).
+  // Per-thread 32-bit byte offsets from the k-tile's (block-uniform) base.
   bf16x8 wreg[WSLOTS_PER_T];
-  auto wstage_load = [&](int cc) {
-    const int c0 = cc * CV_CC;
+  unsigned woff[WSLOTS_PER_T];
 #pragma unroll
-    for (int i = 0; i < WSLOTS_PER_T; ++i) {
-      int s = i * CV_NW * WAVE + tid;
-      if (s < WSLOTS) {
-        int oct = s & 1;
-        int kr = (s >> 1) & (CV_BK - 1);
-        int tap = (s >> 1) >> 6;  // 64 k-rows per tap
-        wreg[i] = *(const bf16x8*)&wr[((long long)tap * Kpad + k0 + kr) * C16 +
-                                      c0 + oct * 8];
-      }
-    }
+  for (int i = 0; i < WSLOTS_PER_T; ++i) {
+    const int s = min(i * CV_NW * WAVE + tid, WSLOTS - 1);
+    const int oct = s & 1;
+    const int kr = (s >> 1) & (CV_BK - 1);
+    const int tap = (s >> 1) >> 6;  // 64 k-rows per tap
+    woff[i] = ((unsigned)(tap * Kpad + kr) * (unsigned)C16 + oct * 8) * 2u;
+  }
+  const char* w_tile = (const char*)(wr + (long long)k0 * C16);
+  auto wstage_load = [&](int cc) {
+    const char* wb = w_tile + cc * (CV_CC * 2);
+#pragma unroll
+    for (int i = 0; i < WSLOTS_PER_T; ++i)
+      wreg[i] = *(const bf16x8*)(wb + woff[i]);
   };
   auto wstage_write = [&]() {
 #pragma unroll
     for (int i = 0; i < WSLOTS_PER_T; ++i) {
-      int s = i * CV_NW * WAVE + tid;
-      if (s < WSLOTS) {
+      const int s = i * CV_NW * WAVE + tid;
+      if ((i + 1) * CV_NW * WAVE <= WSLOTS || s < WSLOTS)
         *(bf16x8*)&wlds[s * 8] = wreg[i];
-      }
     }
   };
 
@@ -198,7 +287,7 @@ __global__ __launch_bounds__(CV_NW * WAVE) void conv3x3_kernel(
   wstage_load(0);
   for (int cc = 0; cc < nc; ++cc) {
     __syncthreads();  // previous compute done; LDS free
-    stage_write();
+    stage_write(cc);
     wstage_write();
     __syncthreads();  // patch + weights ready
     if (cc + 1 < nc) {
@@ -206,16 +295,18 @@ __global__ __launch_bounds__(CV_NW * WAVE) void conv3x3_kernel(
       wstage_load(cc + 1);
     }
 
+    // one base per operand; every tap/row is a compile-time LDS offset
+    const short* wl = &wlds[l31 * CV_CC + hi5 * 8];
+    const short* pl = &patch[(w * RPW * PATCH_C + l31) * CV_CC + hi5 * 8];
 #pragma unroll
     for (int tap = 0; tap < 9; ++tap) {
       const int dy = tap / 3, dx = tap - 3 * (tap / 3);
-      bf16x8 a0 = *(const bf16x8*)&wlds[(tap * CV_BK + l31) * CV_CC + hi5 * 8];
-      bf16x8 a1 = *(const bf16x8*)&wlds[(tap * CV_BK + 32 + l31) * CV_CC + hi5 * 8];
+      bf16x8 a0 = *(const bf16x8*)&wl[tap * CV_BK * CV_CC];
+      bf16x8 a1 = *(const bf16x8*)&wl[(tap * CV_BK + 32) * CV_CC];
 #pragma unroll
       for (int rr = 0; rr < RPW; ++rr) {
-        const int row = w * RPW + rr;
-        bf16x8 b = *(const bf16x8*)&patch[((row + dy) * PATCH_C + l31 + dx) *
-                                              CV_CC + hi5 * 8];
+        bf16x8 b =
+            *(const bf16x8*)&pl[((rr + dy) * PATCH_C + dx) * CV_CC];
         __builtin_amdgcn_s_setprio(1);
         acc[rr][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b, acc[rr][0], 0, 0, 0);
         acc[rr][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b, acc[rr][1], 0, 0, 0);
@@ -224,28 +315,67 @@ __global__ __launch_bounds__(CV_NW * WAVE) void conv3x3_kernel(
     }
   }
 
-  // ---- epilogue: bias (+ residual) add, masked NCHW store.
-  const int x = x0 + l31;
-  if (x < W) {
+  // ---- epilogue: bias (+ residual) add, NCHW store.  RES / EDGE are
+  // block-uniform and decided once, outside: no load sits behind a
+  // per-element condition.  Edge tiles clamp (y, x, k) for the residual
+  // loads and mask the stores; interior tiles have no condition at all.
+  // Offsets inside the block's (n, k0) slab of 64 planes are 32-bit.
+  auto epilogue = [&](auto res_c, auto edge_c) {
+    constexpr bool RES = decltype(res_c)::value;
+    constexpr bool EDGE = decltype(edge_c)::value;
+    // lane coordinates rebuilt from an opaque copy of tid: kept live across
+    // the main loop they cost registers the loop has not got
+    int t = tid;
+    asm volatile("" : "+v"(t));
+    const int w = t / WAVE, l31 = t & 31, hi5 = (t >> 5) & 1;
+    const unsigned hw = (unsigned)H * (unsigned)W;
+    const long long slab = ((long long)n * K + k0) * hw;
+    // block-uniform bases, 32-bit byte offsets
+    const char* resb = RES ? (const char*)(res + slab) : nullptr;
+    char* outb = (char*)(out + slab);
+    const int x = x0 + l31;
+    const int kmax = K - 1 - k0;  // last valid k of this tile (EDGE)
 #pragma unroll
     for (int rr = 0; rr < RPW; ++rr) {
       const int y = y0 + w * RPW + rr;
-      if (y >= H) continue;
+      const bool pix_ok = !EDGE || (y < H && x < W);
+      const unsigned po = EDGE ? (unsigned)min(y, H - 1) * W + min(x, W - 1)
+                               : (unsigned)y * W + x;
 #pragma unroll
       for (int mf = 0; mf < 2; ++mf) {
+        unsigned rv[16];
+        if constexpr (RES) {
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int k = k0 + mf * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi5;
-          if (k < K) {
-            const long long o = ((long long)n * K + k) * H * W +
-                                (long long)y * W + x;
-            float v = acc[rr][mf][r] + bias[k];
-            if (res != nullptr) v += bf2f(res[o]);
-            out[o] = f2bf(v);
+          for (int r = 0; r < 16; ++r) {
+            const int kl = mf * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi5;
+            const unsigned ke = EDGE ? min(kl, kmax) : kl;
+            rv[r] = *(const unsigned short*)(resb + (po + ke * hw) * 2u);
+          }
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+          const f32x4 b4 = *(const f32x4*)&bias_s[mf * 32 + 8 * q + 4 * hi5];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const int r = q * 4 + j;
+            const int kl = mf * 32 + j + 8 * q + 4 * hi5;
+            float v = acc[rr][mf][r] + b4[j];
+            if constexpr (RES) v += bf2f((short)rv[r]);
+            if (!EDGE || (pix_ok && kl <= kmax))
+              *(short*)(outb + (po + (unsigned)kl * hw) * 2u) = f2bf(v);
           }
         }
       }
     }
+  };
+  const bool edge =
+      y0 + CV_ROWS > H || x0 + CV_COLS > W || k0 + CV_BK > K;
+  if (res != nullptr) {
+    if (edge) epilogue(std::true_type{}, std::true_type{});
+    else epilogue(std::true_type{}, std::false_type{});
+  } else {
+    if (edge) epilogue(std::false_type{}, std::true_type{});
+    else epilogue(std::false_type{}, std::false_type{});
   }
 }
 
@@ -258,7 +388,7 @@ extern "C" void conv3x3_bf16(const void* in, const void* wrepack,
   const int Hs = upsample ? H / 2 : H;
   const int Ws = upsample ? W / 2 : W;
   // rows-per-wave A/B (MODAL_AMD_CONV_RPW=4): doubles MFMA per staged
-  // byte/A-read at 2 waves/SIMD occupancy.
+  // byte/A-read at 1 wave/SIMD occupancy.
   static const int rpw = [] {
     const char* e = getenv("MODAL_AMD_CONV_RPW");
     return (e && atoi(e) == 4) ? 4 : 2;

@@ -31,6 +31,12 @@ OCCUPANCY_FLOORS = {
     "paged_prefill_kernelILi64E": 3,   # bf16 and fp8 cache, the forward's 3
     "paged_prefill_kernelILi128E": 2,  # bf16 and fp8 cache, the forward's 2
     "decode_kernel": 2,
+    # conv3x3_kernel<UP, GN, RPW=2>: 64 accumulators + a chunk of staged
+    # loads in flight must stay within 168 registers
+    "conv3x3_kernelILb0ELb0ELi2E": 3,
+    "conv3x3_kernelILb1ELb0ELi2E": 3,
+    "conv3x3_kernelILb0ELb1ELi2E": 3,
+    "conv3x3_kernelILb1ELb1ELi2E": 3,
     "decode_merge_kernel": 4,
 }
 
