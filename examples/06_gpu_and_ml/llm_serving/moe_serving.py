@@ -8,8 +8,10 @@
 # under vLLM).  Same shape here: a routed top-2 MoE Llama variant
 # (`LlamaConfig(n_experts=...)`, `models/llama/model.py:MoEFFN`) rides the
 # SAME continuous-batching engine — paged KV attention is expert-agnostic,
-# each expert's SwiGLU is a dense hipBLASLt GEMM over its routed tokens —
-# so prefix caching / speculation / fp8-KV all compose.
+# so prefix caching / speculation / fp8-KV all compose.  On the GPU the
+# experts run on the fused lane (`moe_impl="fused"`, ops/csrc/moe.hip):
+# routing, the grouped expert GEMMs and the combine stay on the device, so
+# decode replays one captured graph like a dense model.
 
 import modal_examples_amd as modal
 
@@ -32,7 +34,7 @@ class MoELLM:
                else LlamaConfig.moe_small())
         eng = LlamaEngine(cfg, device="cuda" if gpu else "cpu",
                           dtype=torch.bfloat16 if gpu else torch.float32,
-                          use_graph=False,  # expert routing is data-dependent
+                          moe_impl="fused" if gpu else None, use_graph=gpu,
                           kv_blocks=None if gpu else 128, prefix_cache=True)
         self.cfg = cfg
         self.engine = eng

@@ -19,6 +19,7 @@ Sized for 288 GB HBM3E: KV pool defaults to 60% of free memory after weights
 """
 from __future__ import annotations
 
+import dataclasses
 import time
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional
@@ -26,7 +27,7 @@ from typing import Dict, List, Optional
 import torch
 
 from ...ops import functional as OF
-from .model import LlamaConfig, LlamaModel
+from .model import LlamaConfig, LlamaModel, MoEFFN
 
 BLOCK = 16
 
@@ -77,7 +78,8 @@ class LlamaEngine:
                  chunked_prefill: int = 0,
                  prefix_cache: bool = False,
                  gpu_mem_util: float = 0.6,
-                 prefill_attn: str = "decode"):
+                 prefill_attn: str = "decode",
+                 moe_impl: Optional[str] = None):
         """tp: optional parallel.tp.TPGroup — head-sharded tensor parallelism
         (vllm_inference.py:180 --tensor-parallel-size role).  Every rank runs
         the same engine loop on identical requests; the KV cache holds only
@@ -113,10 +115,22 @@ class LlamaEngine:
         row (csrc/attention_prefill_paged.hip).  Monolithic prefill,
         decode and speculative verification are the same under both.
 
+        moe_impl: the forward of an MoE config's expert FFN (MoEFFN):
+        "loop", the host loop over active experts, or "fused", the
+        device-side routed FFN of ops.moe_ffn.  None keeps cfg.moe_impl.
+        The loop reads the routing back to the host, so an MoE engine on it
+        decodes eagerly whatever use_graph says; "fused" captures and
+        replays like a dense model.  Every other lane calls the same FFN.
+
         gpu_mem_util: fraction of free HBM the KV pool claims when
         kv_blocks is unset (--gpu-memory-utilization / --mem-fraction-static
         role, lfm_snapshot.py:316 / deepseek_v4_flash.py:255)."""
         self.cfg = cfg or LlamaConfig.llama3_8b()
+        if moe_impl is not None:
+            self.cfg = dataclasses.replace(self.cfg, moe_impl=moe_impl)
+        if self.cfg.moe_impl not in MoEFFN.IMPLS:
+            raise ValueError(f"moe_impl must be one of {MoEFFN.IMPLS}, got "
+                             f"{self.cfg.moe_impl!r}")
         self.tp = tp
         self.spec_tokens = spec_tokens
         self.spec_proposed = 0   # drafts offered
@@ -141,6 +155,9 @@ class LlamaEngine:
         # full-width decode graph would never replay — don't pay its capture
         self.use_graph = (use_graph and self.device.type == "cuda"
                           and spec_tokens == 0)
+        # the MoE host loop syncs on the routing: it cannot be captured
+        if self.cfg.n_experts > 0 and self.cfg.moe_impl == "loop":
+            self.use_graph = False
         self.eos_id = eos_id
         self.top_p = top_p
         self.seed = seed

@@ -35,6 +35,7 @@ class LlamaConfig:
     max_seq: int = 8192
     n_experts: int = 0   # >0: MoE FFN (Mixtral/DeepSeek-class)
     experts_per_tok: int = 2
+    moe_impl: str = "loop"  # MoEFFN forward: "loop" or "fused" (ops.moe_ffn)
 
     @staticmethod
     def llama3_8b() -> "LlamaConfig":
@@ -74,7 +75,7 @@ class LlamaBlock(nn.Module):
         if cfg.n_experts > 0:
             assert tp_world == 1, "MoE + TP not supported (EP is a non-goal)"
             self.moe = MoEFFN(d, cfg.ffn_dim, cfg.n_experts,
-                              cfg.experts_per_tok)
+                              cfg.experts_per_tok, impl=cfg.moe_impl)
             self.gate_up = self.down = None
         else:
             self.moe = None
@@ -229,10 +230,26 @@ class MoEFFN(nn.Module):
     Router scores per token; top-k experts run their SwiGLU on the tokens
     routed to them (token-dispatch loop: E is small, every expert GEMM is a
     dense hipBLASLt call over its token group; glu_fused reads both halves
-    of the fused gate_up in place)."""
+    of the fused gate_up in place).
 
-    def __init__(self, dim: int, ffn_dim: int, n_experts: int, top_k: int):
+    impl="loop" (default) is that host loop: it reads the routing back to
+    the host in every call, so it cannot be captured into a graph.
+    impl="fused" is router -> ops.moe_route -> ops.moe_ffn: routing, the
+    grouped-GEMM schedule, both expert GEMMs and the combine stay on the
+    device (csrc/moe.hip), sync-free and capturable; the routing weights
+    stay fp32 and each token's expert outputs are summed in fp32.  Shared
+    experts, expert parallelism and fp8 expert weights are not supported by
+    either."""
+
+    IMPLS = ("loop", "fused")
+
+    def __init__(self, dim: int, ffn_dim: int, n_experts: int, top_k: int,
+                 impl: str = "loop"):
         super().__init__()
+        if impl not in self.IMPLS:
+            raise ValueError(f"moe impl must be one of {self.IMPLS}, got "
+                             f"{impl!r}")
+        self.impl = impl
         self.router = nn.Linear(dim, n_experts, bias=False)
         self.gate_up = nn.Parameter(
             torch.empty(n_experts, 2 * ffn_dim, dim).normal_(std=0.02))
@@ -246,6 +263,10 @@ class MoEFFN(nn.Module):
         B, S, d = x.shape
         flat = x.reshape(-1, d)
         scores = self.router(flat).float()                  # [N, E]
+        if self.impl == "fused":
+            w, idx = OF.moe_route(scores, self.top_k)
+            return OF.moe_ffn(flat.contiguous(), self.gate_up, self.down, w,
+                              idx).view(B, S, d)
         w, idx = scores.topk(self.top_k, dim=-1)            # [N, k]
         w = torch.softmax(w, dim=-1).to(x.dtype)
         out = torch.zeros_like(flat)

@@ -29,6 +29,7 @@ HIP_SOURCES = [
     "adamw.hip",
     "sampling.hip",
     "conv3x3.hip",
+    "moe.hip",
 ]
 
 

@@ -67,6 +67,14 @@ void conv3x3_bf16(const void*, const void*, const void*, const void*, void*,
 void gn_conv_coeffs_bf16(const void*, float*, const float*, const float*,
                          float*, float*, int, int, int, long long, int, float,
                          hipStream_t);
+// the MoE launchers return 0 once launched, non-zero (nothing launched)
+// for a shape they do not support
+int moe_max_tiles(long long, int, int);
+int moe_route_f32(const float*, float*, int*, long long, int, int,
+                  hipStream_t);
+int moe_ffn_bf16(const void*, const void*, const void*, const float*,
+                 const int*, int*, void*, float*, void*, long long, int, int,
+                 int, int, hipStream_t);
 }
 
 namespace {
@@ -561,6 +569,88 @@ torch::Tensor conv3x3_gn(torch::Tensor x, torch::Tensor wr, torch::Tensor bias,
   return out;
 }
 
+// ---------------------------------------------------------------- MoE FFN
+// Supported: E <= 128, 1 <= top_k <= min(E, 8), dim and ffn_dim multiples of
+// 64, any N >= 1.  Every check raises before anything is launched; every
+// workspace size depends on shapes only, so both entries capture into a graph.
+
+std::tuple<torch::Tensor, torch::Tensor> moe_route(torch::Tensor logits,
+                                                   int64_t top_k) {
+  TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == torch::kFloat32 &&
+                  logits.dim() == 2 && logits.is_contiguous(),
+              "moe_route: logits must be fp32 [N,E] contiguous on GPU");
+  const int64_t N = logits.size(0), E = logits.size(1);
+  TORCH_CHECK(N >= 1, "moe_route: logits has no rows");
+  TORCH_CHECK(E >= 1 && E <= 128, "moe_route: logits has E=", E,
+              " experts (supported: 1..128)");
+  TORCH_CHECK(top_k >= 1 && top_k <= 8 && top_k <= E, "moe_route: top_k=",
+              top_k, " (supported: 1..min(E, 8), E=", E, ")");
+  auto w = torch::empty({N, top_k}, logits.options());
+  auto idx = torch::empty({N, top_k}, logits.options().dtype(torch::kInt32));
+  int rc = moe_route_f32(logits.data_ptr<float>(), w.data_ptr<float>(),
+                         idx.data_ptr<int>(), N, (int)E, (int)top_k,
+                         cur_stream());
+  TORCH_CHECK(rc == 0, "moe_route: logits shape ", logits.sizes(),
+              " with top_k=", top_k, " not supported by the kernel");
+  return {w, idx};
+}
+
+// x [N,d], gate_up [E,2F,d], down [E,d,F] bf16; weights fp32 / idx int32
+// [N,k], idx in [0,E) and distinct per token (a precondition: only the
+// device sees the values).  Returns [N,d] bf16.
+torch::Tensor moe_ffn(torch::Tensor x, torch::Tensor gate_up,
+                      torch::Tensor down, torch::Tensor weights,
+                      torch::Tensor idx) {
+  check_bf16(x, "x");
+  check_bf16(gate_up, "gate_up");
+  check_bf16(down, "down");
+  TORCH_CHECK(x.dim() == 2 && gate_up.dim() == 3 && down.dim() == 3,
+              "moe_ffn: x must be [N,dim], gate_up [E,2*ffn_dim,dim], down "
+              "[E,dim,ffn_dim]");
+  const int64_t N = x.size(0), d = x.size(1), E = gate_up.size(0),
+                F = down.size(2);
+  TORCH_CHECK(N >= 1, "moe_ffn: x has no rows");
+  TORCH_CHECK(d >= 64 && d % 64 == 0, "moe_ffn: x has dim=", d,
+              " (must be a multiple of 64)");
+  TORCH_CHECK(F >= 64 && F % 64 == 0, "moe_ffn: down has ffn_dim=", F,
+              " (must be a multiple of 64)");
+  TORCH_CHECK(E >= 1 && E <= 128, "moe_ffn: gate_up has E=", E,
+              " experts (supported: 1..128)");
+  TORCH_CHECK(gate_up.size(1) == 2 * F && gate_up.size(2) == d &&
+                  down.size(0) == E && down.size(1) == d,
+              "moe_ffn: gate_up ", gate_up.sizes(), " / down ", down.sizes(),
+              " do not match [E,2*ffn_dim,dim] / [E,dim,ffn_dim] with dim=",
+              d);
+  TORCH_CHECK(idx.is_cuda() && idx.scalar_type() == torch::kInt32 &&
+                  idx.dim() == 2 && idx.size(0) == N && idx.is_contiguous(),
+              "moe_ffn: idx must be int32 [N,top_k] contiguous on GPU");
+  const int64_t k = idx.size(1);
+  TORCH_CHECK(k >= 1 && k <= 8 && k <= E, "moe_ffn: idx has top_k=", k,
+              " (supported: 1..min(E, 8), E=", E, ")");
+  TORCH_CHECK(weights.is_cuda() && weights.scalar_type() == torch::kFloat32 &&
+                  weights.sizes() == idx.sizes() && weights.is_contiguous(),
+              "moe_ffn: weights must be fp32 [N,top_k] contiguous on GPU");
+  for (const torch::Tensor* t : {&gate_up, &down, &weights, &idx})
+    TORCH_CHECK(t->device() == x.device(),
+                "moe_ffn: all tensors must be on x's device");
+  TORCH_CHECK(N * k < (1ll << 30) && N * k * d < (1ll << 40),
+              "moe_ffn: x has too many rows (N=", N, ")");
+  const int64_t tiles = moe_max_tiles(N, (int)k, (int)E);
+  auto iopt = x.options().dtype(torch::kInt32);
+  auto sched = torch::empty({tiles * 32 + tiles + 1}, iopt);
+  auto h = torch::empty({tiles * 32, F}, x.options());
+  auto y = torch::empty({N * k, d}, x.options().dtype(torch::kFloat32));
+  auto out = torch::empty({N, d}, x.options());
+  int rc = moe_ffn_bf16(x.data_ptr(), gate_up.data_ptr(), down.data_ptr(),
+                        weights.data_ptr<float>(), idx.data_ptr<int>(),
+                        sched.data_ptr<int>(), h.data_ptr(),
+                        y.data_ptr<float>(), out.data_ptr(), N, (int)d,
+                        (int)F, (int)E, (int)k, cur_stream());
+  TORCH_CHECK(rc == 0, "moe_ffn: shape not supported by the kernel (N=", N,
+              " dim=", d, " ffn_dim=", F, " E=", E, " top_k=", k, ")");
+  return out;
+}
+
 torch::Tensor sample_gumbel(torch::Tensor logits, double temperature,
                             int64_t seed) {
   TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == torch::kFloat32,
@@ -761,6 +851,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("conv3x3", &conv3x3, "NCHW implicit-GEMM 3x3 conv, fused bias+res (K3)");
   m.def("conv3x3_gn", &conv3x3_gn, "GroupNorm+SiLU fused into the K3 conv");
   m.def("softmax_fwd", &softmax_fwd);
+  m.def("moe_route", &moe_route,
+        "MoE top-k routing: (weights fp32 [N,k], idx int32 [N,k])");
+  m.def("moe_ffn", &moe_ffn,
+        "fused MoE FFN: on-device schedule, grouped MFMA GEMMs, combine");
   m.def("scale_in_dev", &scale_in_dev, "x * 1/sqrt(sigma^2+1), device sigma");
   m.def("cfg_euler_dev", &cfg_euler_dev, "graph-capturable CFG+Euler step");
   m.def("step_advance", &step_advance, "increment device step counter");

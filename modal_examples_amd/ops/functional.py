@@ -483,3 +483,89 @@ def softmax(x):
     if ext is None:
         return torch.softmax(x.float(), dim=-1)
     return ext.softmax_fwd(x.float().contiguous())
+
+
+# ---- mixture-of-experts FFN.  Supported shapes (csrc/moe.hip): E <= 128,
+# 1 <= top_k <= min(E, 8), dim and ffn_dim multiples of 64, any N >= 1,
+# contiguous operands.  The checks below run on every device, before the
+# dispatch, so the reference path refuses exactly what the kernel refuses.
+
+def _check_moe_route(logits, top_k):
+    if logits.dim() != 2 or logits.shape[0] < 1:
+        raise ValueError(f"logits must be [N, E] with N >= 1, got "
+                         f"{tuple(logits.shape)}")
+    E = logits.shape[1]
+    if not 1 <= E <= 128:
+        raise ValueError(f"logits has E={E} experts (supported: 1..128)")
+    if not isinstance(top_k, int) or not 1 <= top_k <= min(E, 8):
+        raise ValueError(f"top_k={top_k!r} (supported: 1..min(E, 8) = "
+                         f"{min(E, 8)})")
+
+
+def moe_route(logits, top_k: int):
+    """Top-k expert routing.  logits [N, E] -> (weights [N, k] fp32, idx
+    [N, k] int32): the k largest logits per row in descending order, ties to
+    the lower expert index; weights = softmax over those k logits.  One
+    kernel, nothing read back to the host."""
+    _check_moe_route(logits, top_k)
+    ext = _ext_for(logits, any_dtype=True)
+    if ext is None:
+        return ref.moe_route_ref(logits, top_k)
+    return ext.moe_route(logits.float().contiguous(), top_k)
+
+
+def _check_moe_ffn(x, gate_up, down, weights, idx):
+    if x.dim() != 2 or x.shape[0] < 1:
+        raise ValueError(f"x must be [N, dim] with N >= 1, got "
+                         f"{tuple(x.shape)}")
+    N, d = x.shape
+    if d % 64 != 0:
+        raise ValueError(f"x has dim={d} (must be a multiple of 64)")
+    if gate_up.dim() != 3 or gate_up.shape[2] != d \
+            or gate_up.shape[1] % 2 != 0:
+        raise ValueError(f"gate_up must be [E, 2*ffn_dim, dim={d}], got "
+                         f"{tuple(gate_up.shape)}")
+    E, F = gate_up.shape[0], gate_up.shape[1] // 2
+    if not 1 <= E <= 128:
+        raise ValueError(f"gate_up has E={E} experts (supported: 1..128)")
+    if F % 64 != 0 or F < 64:
+        raise ValueError(f"gate_up has ffn_dim={F} (must be a multiple of "
+                         f"64)")
+    if tuple(down.shape) != (E, d, F):
+        raise ValueError(f"down must be [E={E}, dim={d}, ffn_dim={F}], got "
+                         f"{tuple(down.shape)}")
+    if idx.dtype is not torch.int32:
+        raise TypeError(f"idx must be int32, got {idx.dtype}")
+    if idx.dim() != 2 or idx.shape[0] != N \
+            or not 1 <= idx.shape[1] <= min(E, 8):
+        raise ValueError(f"idx must be [N={N}, top_k] with top_k in "
+                         f"1..min(E, 8) = {min(E, 8)}, got {tuple(idx.shape)}")
+    if weights.shape != idx.shape:
+        raise ValueError(f"weights must have idx's shape "
+                         f"{tuple(idx.shape)}, got {tuple(weights.shape)}")
+    for name, t in (("x", x), ("gate_up", gate_up), ("down", down)):
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+        if t.dtype is not x.dtype or t.device != x.device:
+            raise ValueError(f"{name} must have x's dtype and device "
+                             f"({x.dtype}, {x.device}), got {t.dtype}, "
+                             f"{t.device}")
+
+
+def moe_ffn(x, gate_up, down, weights, idx):
+    """Routed SwiGLU FFN over E experts, fused (csrc/moe.hip):
+    out[t] = sum_j weights[t, j] * FFN_{idx[t, j]}(x[t]).
+
+    x [N, dim]; gate_up [E, 2*ffn_dim, dim] (gate rows, then up rows); down
+    [E, dim, ffn_dim]; weights fp32 / idx int32 [N, k] as moe_route returns
+    them.  Precondition: idx values in [0, E) and distinct per token —
+    moe_route always satisfies it; the values are never read on the host.
+    On the GPU nothing depends on the routing but the data, so the call
+    captures into a graph; the result is bitwise reproducible.  Returns
+    [N, dim] in x's dtype."""
+    _check_moe_ffn(x, gate_up, down, weights, idx)
+    ext = _ext_for(x, gate_up, down, weights)
+    if ext is None:
+        return ref.moe_ffn_ref(x, gate_up, down, weights, idx)
+    return ext.moe_ffn(x, gate_up, down, weights.float().contiguous(),
+                       idx.contiguous())

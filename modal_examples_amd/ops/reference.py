@@ -320,3 +320,35 @@ def sample_batch_ref(logits, temperature, top_k, top_p, min_p, seeds, counters):
     scores = gumbel_scores_ref(lg, safe_t, seeds, counters)
     scores = scores.masked_fill(~(lg >= cut[:, None]), float("-inf"))
     return torch.where(live, scores.argmax(-1), lg.argmax(-1)).int()
+
+
+def moe_route_ref(logits, top_k: int):
+    """Top-k routing: (weights [N,k], idx int32 [N,k]).  A STABLE descending
+    sort defines the order — descending logit, ties to the lower expert
+    index; weights are the softmax over the k selected logits, in the
+    logits' working precision (gradients flow to them)."""
+    vals, order = torch.sort(_wide(logits), dim=-1, descending=True,
+                             stable=True)
+    return (torch.softmax(vals[:, :top_k], dim=-1),
+            order[:, :top_k].to(torch.int32))
+
+
+def moe_ffn_ref(x, gate_up, down, weights, idx):
+    """Routed SwiGLU FFN: out[t] = sum_j weights[t,j] * FFN_{idx[t,j]}(x[t])
+    with FFN_e(v) = (silu(v @ gate_e^T) * (v @ up_e^T)) @ down_e^T, where
+    gate_e / up_e are the two halves of gate_up[e] [2F, d] and down[e] is
+    [d, F].  Working-precision math with no data-dependent control flow:
+    every expert runs on every token and the routing enters as a dense
+    [N, E] coefficient matrix, so it is differentiable in x, the weights
+    and the routing weights, and costs E/k times the routed FLOPs.  Returns
+    [N, d] in x's dtype."""
+    E, F = gate_up.shape[0], down.shape[2]
+    xw, ww = _wide(x), _wide(weights).to(_wide(x).dtype)
+    coef = torch.zeros(x.shape[0], E, dtype=xw.dtype, device=x.device)
+    coef = coef.scatter_add(1, idx.long(), ww)
+    out = torch.zeros_like(xw)
+    for e in range(E):
+        gu = xw @ _wide(gate_up[e]).T
+        h = torch.nn.functional.silu(gu[:, :F]) * gu[:, F:]
+        out = out + coef[:, e:e + 1] * (h @ _wide(down[e]).T)
+    return out.to(x.dtype)

@@ -38,6 +38,16 @@ OCCUPANCY_FLOORS = {
     "conv3x3_kernelILb0ELb1ELi2E": 3,
     "conv3x3_kernelILb1ELb1ELi2E": 3,
     "decode_merge_kernel": 4,
+    # moe_gemm_kernel<UP, NF>: two register sets of NF-step chunks in flight
+    # beside 32 accumulators; one wave per SIMD already covers the decode
+    # case (a wave per 32x64 output tile), the floors guard the rest
+    "moe_gemm_kernelILb1ELi8E": 1,   # up GEMM, 128-deep chunks
+    "moe_gemm_kernelILb1ELi4E": 2,   # up GEMM, 64-deep chunks
+    "moe_gemm_kernelILb0ELi8E": 2,   # down GEMM, 128-deep chunks
+    "moe_gemm_kernelILb0ELi4E": 2,   # down GEMM, 64-deep chunks
+    "moe_route_kernel": 8,
+    "moe_align_kernel": 8,
+    "moe_combine_kernel": 8,
 }
 
 
