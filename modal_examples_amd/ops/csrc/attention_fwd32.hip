@@ -196,18 +196,25 @@ void fa32_kernel(
 
   // ---- epilogue: O[q][d] = O^T[d][q] / l ----
   if (my_q < Sq) {
+    // A causal row before the first key (Sq > Sk) sees nothing: o = 0 and
+    // lse = -inf.  In a q block that still has live rows the loop ran with
+    // every score of such a row at -1e30, which leaves the mean of a KV
+    // block in acc, so the row is overridden here, not in the loop.
+    const bool hidden = CAUSAL && my_q + causal_off < 0;
     // log-sum-exp of the scaled scores for the backward: l_run is always
     // sum exp(s - m_run), with defer-max on or off.  Both lane halves hold
     // the same pair; the low half writes.
     if (LSE != nullptr && hi5 == 0)
-      LSE[((long long)b * Hq + h) * Sq + my_q] = m_run + logf(l_run);
+      LSE[((long long)b * Hq + h) * Sq + my_q] =
+          hidden ? -INFINITY : m_run + logf(l_run);
     float inv = l_run > 0.f ? 1.f / l_run : 0.f;
 #pragma unroll
     for (int dt = 0; dt < DT; ++dt)
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         int d = dt * 32 + c_row(r, hi5);
-        O[ooff + (long long)my_q * st.o.s + d] = f2bf(acc[dt][r] * inv);
+        O[ooff + (long long)my_q * st.o.s + d] =
+            f2bf(hidden ? 0.f : acc[dt][r] * inv);
       }
   }
 }

@@ -132,16 +132,49 @@ void push_strides(std::vector<long long>& st, const torch::Tensor& t) {
 // Whisper blocks) skip every transpose copy around the kernel.  with_lse
 // (training) also returns the fp32 log-sum-exp per query row [B,Hq,Sq] that
 // the backward recomputes P from.  Unsupported configurations raise here,
-// before anything is launched.
+// before anything is launched: no key at all (Sk == 0) is an error, no
+// query at all (B, Hq or Sq zero) returns the empty tensors without a launch.
+// out / lse_out, when given, are written instead of fresh tensors and
+// returned: out bf16 of the output's shape with any strides (d contiguous),
+// lse_out fp32 [B,Hq,Sq] contiguous.
 std::tuple<torch::Tensor, torch::Tensor> attention_fwd(
     const torch::Tensor& q, const torch::Tensor& k, const torch::Tensor& v,
-    bool causal, double scale, bool bshd, bool with_lse) {
+    bool causal, double scale, bool bshd, bool with_lse,
+    const c10::optional<torch::Tensor>& out = c10::nullopt,
+    const c10::optional<torch::Tensor>& lse_out = c10::nullopt) {
   const AttnDims d = check_qkv("attention", q, k, v);
-  auto o = bshd ? torch::empty({d.B, d.Sq, d.Hq, d.D}, q.options())
-                : torch::empty(q.sizes(), q.options());
+  TORCH_CHECK(d.Sk >= 1, "attention: Sk must be at least 1, got Sk=", d.Sk,
+              " (a query with no key has no softmax)");
+  const std::vector<int64_t> o_shape =
+      bshd ? std::vector<int64_t>{d.B, d.Sq, d.Hq, d.D}
+           : std::vector<int64_t>{d.B, d.Hq, d.Sq, d.D};
+  torch::Tensor o;
+  if (out.has_value()) {
+    o = *out;
+    TORCH_CHECK(o.device() == q.device() && o.scalar_type() == torch::kBFloat16 &&
+                o.sizes() == torch::IntArrayRef(o_shape) &&
+                (o.numel() == 0 || o.stride(3) == 1),
+                "attention: out must be bf16 on the GPU with the output's "
+                "shape ", torch::IntArrayRef(o_shape), " and head_dim "
+                "contiguous");
+  } else {
+    o = torch::empty(o_shape, q.options());
+  }
   torch::Tensor lse;
-  if (with_lse)
-    lse = torch::empty({d.B, d.Hq, d.Sq}, q.options().dtype(torch::kFloat32));
+  if (with_lse) {
+    if (lse_out.has_value()) {
+      lse = *lse_out;
+      TORCH_CHECK(lse.device() == q.device() && lse.scalar_type() == torch::kFloat32 &&
+                  lse.dim() == 3 && lse.size(0) == d.B &&
+                  lse.size(1) == d.Hq && lse.size(2) == d.Sq &&
+                  lse.is_contiguous(),
+                  "attention: lse must be fp32 [B,Hq,Sq] contiguous");
+    } else {
+      lse = torch::empty({d.B, d.Hq, d.Sq},
+                         q.options().dtype(torch::kFloat32));
+    }
+  }
+  if (o.numel() == 0) return {o, lse};  // a zero grid dimension is no launch
   std::vector<long long> st;
   for (const auto& t : {q, k, v, bshd ? o.transpose(1, 2) : o})
     push_strides(st, t);
@@ -170,14 +203,16 @@ torch::Tensor attention_bshd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
 
 std::tuple<torch::Tensor, torch::Tensor> attention_fwd_lse(
     torch::Tensor q, torch::Tensor k, torch::Tensor v, bool causal,
-    double scale) {
-  return attention_fwd(q, k, v, causal, scale, false, true);
+    double scale, c10::optional<torch::Tensor> out,
+    c10::optional<torch::Tensor> lse) {
+  return attention_fwd(q, k, v, causal, scale, false, true, out, lse);
 }
 
 std::tuple<torch::Tensor, torch::Tensor> attention_fwd_lse_bshd(
     torch::Tensor q, torch::Tensor k, torch::Tensor v, bool causal,
-    double scale) {
-  return attention_fwd(q, k, v, causal, scale, true, true);
+    double scale, c10::optional<torch::Tensor> out,
+    c10::optional<torch::Tensor> lse) {
+  return attention_fwd(q, k, v, causal, scale, true, true, out, lse);
 }
 
 torch::Tensor paged_decode(torch::Tensor q, torch::Tensor kc, torch::Tensor vc,
@@ -824,9 +859,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("attention", &attention, "flash attention fwd bf16 (K1/K5/K7)");
   m.def("attention_bshd", &attention_bshd, "stride-aware attention, BSHD out");
   m.def("attention_fwd_lse", &attention_fwd_lse,
-        "attention fwd returning (o, lse) for the backward");
+        "attention fwd returning (o, lse) for the backward; out= / lse= "
+        "write into the caller's tensors",
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"),
+        py::arg("scale"), py::arg("out") = py::none(),
+        py::arg("lse") = py::none());
   m.def("attention_fwd_lse_bshd", &attention_fwd_lse_bshd,
-        "attention fwd returning (o [B,S,H,D], lse)");
+        "attention fwd returning (o [B,S,H,D], lse); out= / lse= write into "
+        "the caller's tensors",
+        py::arg("q"), py::arg("k"), py::arg("v"), py::arg("causal"),
+        py::arg("scale"), py::arg("out") = py::none(),
+        py::arg("lse") = py::none());
   m.def("attention_bwd", &attention_bwd,
         "flash attention bwd bf16 into caller-provided dq/dk/dv");
   m.def("paged_decode", &paged_decode, "paged KV decode attention (K6)");

@@ -116,6 +116,9 @@ def _attention(q, k, v, causal, scale, bshd: bool):
     with any strides; bshd=True returns o as [B,S,H,D] and hands the kernel
     the strided views as they are, bshd=False returns [B,H,S,D]."""
     scale = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
+    if k.shape[2] == 0:
+        raise ValueError("attention: Sk must be at least 1, got Sk=0 (a query "
+                         "with no key has no softmax)")
     ext = _attn_train_ext(q, k, v, causal)
     if ext is not None:
         return _AttentionFn.apply(q, k, v, causal, scale, bshd, ext)
@@ -131,7 +134,13 @@ def _attention(q, k, v, causal, scale, bshd: bool):
 
 def attention(q, k, v, causal: bool = False, scale: Optional[float] = None):
     """Flash attention (K1/K5/K7). q [B,Hq,Sq,D], k/v [B,Hkv,Sk,D] bf16.
-    Differentiable on the GPU through the HIP backward."""
+    Differentiable on the GPU through the HIP backward.
+
+    causal aligns the mask to the last key: row i sees keys <= i + Sk - Sq.
+    With Sq > Sk the first Sq - Sk rows see no key and return exactly 0
+    (their saved log-sum-exp is -inf, their gradients are 0; grad mode takes
+    the reference path for this configuration).  No query at all (B, Hq or
+    Sq zero) returns the empty tensor without a launch; Sk == 0 raises."""
     return _attention(q, k, v, causal, scale, False)
 
 
@@ -143,7 +152,8 @@ def attention_qkv(q, k, v, causal: bool = False, scale: Optional[float] = None):
     ready for the output projection.  On GPU the kernel reads the strided
     layouts directly and writes BSHD — no .contiguous() copies at all; in
     grad mode the backward reads the same views and the [B,S,Hq*D] output
-    gradient in place.
+    gradient in place.  Rows that see no key (causal, S > Sk), empty inputs
+    and Sk == 0 behave as in `attention`.
     """
     B, S, Hq, D = q.shape
     o = _attention(q.transpose(1, 2), k.transpose(1, 2), v.transpose(1, 2),

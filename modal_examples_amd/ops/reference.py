@@ -14,7 +14,11 @@ import torch
 
 
 def attention_ref(q, k, v, causal: bool = False, scale: Optional[float] = None):
-    """q [B,Hq,Sq,D], k/v [B,Hkv,Sk,D] → [B,Hq,Sq,D]; GQA by head repeat."""
+    """q [B,Hq,Sq,D], k/v [B,Hkv,Sk,D] → [B,Hq,Sq,D]; GQA by head repeat.
+
+    The causal mask is aligned to the last key (offset Sk - Sq).  With
+    Sq > Sk the first Sq - Sk query rows see no key: their output is zero,
+    and so are their gradients."""
     B, Hq, Sq, D = q.shape
     Hkv, Sk = k.shape[1], k.shape[2]
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
@@ -24,11 +28,19 @@ def attention_ref(q, k, v, causal: bool = False, scale: Optional[float] = None):
         kf = kf.repeat_interleave(rep, dim=1)
         vf = vf.repeat_interleave(rep, dim=1)
     s = torch.matmul(qf, kf.transpose(-1, -2)) * scale
+    hidden = None
     if causal:
         off = Sk - Sq
         mask = torch.ones(Sq, Sk, dtype=torch.bool, device=q.device).tril(off)
         s = s.masked_fill(~mask, float("-inf"))
+        if off < 0:
+            # rows that see nothing: finite scores through the softmax (an
+            # all -inf row is NaN, forward and backward), then P = 0
+            hidden = ~mask.any(-1, keepdim=True)
+            s = s.masked_fill(hidden, 0.0)
     p = torch.softmax(s, dim=-1)
+    if hidden is not None:
+        p = p.masked_fill(hidden, 0.0)
     return torch.matmul(p, vf).to(q.dtype)
 
 
@@ -54,11 +66,46 @@ def _masked_scores(q, k, causal, scale):
 def attention_lse_ref(q, k, causal: bool = False,
                       scale: Optional[float] = None):
     """Log-sum-exp of the scaled, masked scores per query row: [B,Hq,Sq] in
-    the working precision — what the forward kernel saves for the backward."""
+    the working precision — what the forward kernel saves for the backward.
+    A row that sees no key (causal with Sq > Sk) has -inf."""
     B, Hq, Sq, D = q.shape
     scale = scale if scale is not None else 1.0 / math.sqrt(D)
     s = _masked_scores(q, k, causal, scale)
     return torch.logsumexp(s, dim=-1).reshape(B, Hq, Sq)
+
+
+def attention_fwd_ref(q, k, v, causal: bool = False,
+                      scale: Optional[float] = None,
+                      emulate_bf16: bool = False):
+    """Attention forward as csrc/attention_fwd32.hip computes it, and its
+    specification: P = exp(s - rowmax), o = (P.V) / rowsum(P), lse = rowmax +
+    log(rowsum(P)).  q [B,Hq,Sq,D], k/v [B,Hkv,Sk,D]; returns (o [B,Hq,Sq,D],
+    lse [B,Hq,Sq]) in the working precision (fp64 for fp64 inputs).  A row
+    that sees no key (causal with Sq > Sk) has o = 0 and lse = -inf.
+
+    emulate_bf16=True rounds exactly where the kernel rounds: P to bf16
+    before P.V, normalised by the unrounded row sum, and the output to bf16
+    (returned widened).  The caller passes bf16-representable q/k/v for a
+    faithful yardstick."""
+    B, Hq, Sq, D = q.shape
+    Hkv = k.shape[1]
+    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    wd = torch.float64 if q.dtype is torch.float64 else torch.float32
+
+    def rnd(t):
+        return t.to(torch.bfloat16).to(wd) if emulate_bf16 else t
+
+    s = _masked_scores(q, k, causal, scale)  # [B,Hkv,G,Sq,Sk]
+    m = s.amax(-1, keepdim=True)
+    live = m > float("-inf")
+    m = torch.where(live, m, torch.zeros_like(m))
+    p = torch.exp(s - m)  # masked -> 0
+    l = p.sum(-1, keepdim=True)
+    lse = (m + torch.log(l)).reshape(B, Hq, Sq)
+    o = torch.matmul(rnd(p), _wide(v).unsqueeze(2))
+    o = torch.where(live, o / torch.where(live, l, torch.ones_like(l)),
+                    torch.zeros_like(o))
+    return rnd(o).reshape(B, Hq, Sq, D), lse
 
 
 def attention_bwd_ref(q, k, v, o, lse, dout, causal: bool = False,

@@ -2,6 +2,13 @@
 
 Run on a real MI355X via:  gpurun -- 'python -m pytest tests -m gpu -x -q'
 Tolerances reflect bf16 I/O with f32 accumulation.
+
+The test_attention_* functions here are the loose tier for the attention
+forward.  The strict tier — bitwise selector cases, an fp64 truth with a
+bf16-emulating yardstick on every element, masks, GQA mapping, stray writes,
+hidden rows, empty inputs and the no-defer instantiations — is
+test_attention_forward.py (CPU: builders, judge, mutants) and
+test_attention_forward_gpu.py.
 """
 import math
 
