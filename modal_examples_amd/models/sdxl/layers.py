@@ -68,9 +68,12 @@ class GroupNormSiLU(nn.Module, _F32ParamCache):
         self.eps = eps
         self.silu = silu
 
-    def forward(self, x):
+    def forward(self, x, out_nhwc: bool = False):
+        """out_nhwc=True returns [B, H*W, C] (the kernel writes that layout
+        itself) for the sequence-major sections that follow a GroupNorm."""
         return OF.groupnorm_silu(x, self._f32("weight"), self._f32("bias"),
-                                 self.groups, self.eps, self.silu)
+                                 self.groups, self.eps, self.silu,
+                                 out_nhwc=out_nhwc)
 
 
 class Conv3x3(nn.Conv2d):
@@ -118,14 +121,20 @@ class Conv3x3(nn.Conv2d):
                                  raw_weight=self.weight, upsample=upsample)
         return self.forward(gn(x), residual=residual, upsample=upsample)
 
-    def forward(self, x, residual=None, upsample: bool = False):
+    def forward(self, x, residual=None, upsample: bool = False, addend=None):
+        """addend [N, K]: one value per (image, output channel), added to the
+        conv output in the kernel's epilogue (the resnets' time-embedding
+        projection); a plain broadcast add off the kernel path."""
         if self._use_kernel(x):
             wr, b = self._packed()
             return OF.conv3x3(x, wr, b, self.out_channels, residual=residual,
-                              raw_weight=self.weight, upsample=upsample)
+                              raw_weight=self.weight, upsample=upsample,
+                              addend=addend)
         if upsample:
             x = nn.functional.interpolate(x, scale_factor=2.0, mode="nearest")
         y = nn.functional.conv2d(x, self.weight, self.bias, padding=1)
+        if addend is not None:
+            y = y + addend[:, :, None, None]
         return y if residual is None else y + residual
 
 
@@ -195,7 +204,12 @@ class GEGLUFeedForward(nn.Module):
 
 class TransformerBlock(nn.Module):
     """ln→self-attn→ln→cross-attn→ln→GEGLU-FF, pre-norm residuals (the
-    diffusers BasicTransformerBlock shape exercised at text_to_image.py:114)."""
+    diffusers BasicTransformerBlock shape exercised at text_to_image.py:114).
+
+    In inference the first two residual adds run fused with the LayerNorm
+    that follows them (OF.add_layernorm: one read of the two addends yields
+    both x and LN(x)); the third add stays on its own.  Training and autograd
+    run the separate ops inside OF.add_layernorm."""
 
     def __init__(self, dim: int, ctx_dim: int, head_dim: int = 64):
         super().__init__()
@@ -207,10 +221,14 @@ class TransformerBlock(nn.Module):
         self.ff = GEGLUFeedForward(dim)
 
     def forward(self, x, ctx):
-        x = x + self.attn1(self.norm1(x))
-        x = x + self.attn2(self.norm2(x), ctx)
-        x = x + self.ff(self.norm3(x))
-        return x
+        # off the kernel path (CPU, fp32, autograd) add_layernorm is the
+        # plain `x = x + y` followed by layernorm(x)
+        n2, n3 = self.norm2, self.norm3
+        x, h = OF.add_layernorm(x, self.attn1(self.norm1(x)),
+                                n2._f32("weight"), n2._f32("bias"), n2.eps)
+        x, h = OF.add_layernorm(x, self.attn2(h, ctx),
+                                n3._f32("weight"), n3._f32("bias"), n3.eps)
+        return x + self.ff(h)
 
 
 def timestep_embedding(t: torch.Tensor, dim: int, max_period: float = 10000.0):

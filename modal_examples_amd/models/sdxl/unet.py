@@ -19,6 +19,7 @@ from dataclasses import dataclass
 import torch
 import torch.nn as nn
 
+from ...ops import functional as OF
 from .layers import (
     Conv1x1,
     Conv3x3,
@@ -67,14 +68,20 @@ class ResnetBlock(nn.Module):
 
     def forward(self, x, temb):
         # GN+SiLU stays a separate two-pass kernel: fusing it into conv
-        # staging re-runs the exp per output-k-tile (measured 13.3->9.4 img/s)
-        h = self.conv1(self.norm1(x))
-        h = h + self.temb_proj(torch.nn.functional.silu(temb))[:, :, None, None]
+        # staging re-runs the exp per output-k-tile (measured 13.3->9.4 img/s).
+        # The time-embedding projection, one value per (image, channel), is
+        # added in conv1's epilogue: no pass over h between conv1 and norm2.
+        t = self.temb_proj(torch.nn.functional.silu(temb))
+        h = self.conv1(self.norm1(x), addend=t)
         return self.conv2(self.norm2(h), residual=self.skip(x))
 
 
 class SpatialTransformer(nn.Module):
-    """GN → 1x1 proj_in → depth× TransformerBlock over flattened HW → proj_out."""
+    """GN → 1x1 proj_in → depth× TransformerBlock over flattened HW → proj_out.
+
+    The GroupNorm kernel writes the [B, HW, C] layout the blocks take, and one
+    tiled-transpose kernel adds the [B, HW, C] result back onto the NCHW
+    residual: no transposing copy on the way in or out."""
 
     def __init__(self, channels: int, depth: int, ctx_dim: int, head_dim: int):
         super().__init__()
@@ -86,14 +93,10 @@ class SpatialTransformer(nn.Module):
         self.proj_out = nn.Linear(channels, channels)
 
     def forward(self, x, ctx):
-        B, C, H, W = x.shape
-        res = x
-        h = self.norm(x).permute(0, 2, 3, 1).reshape(B, H * W, C)
-        h = self.proj_in(h)
+        h = self.proj_in(self.norm(x, out_nhwc=True))
         for blk in self.blocks:
             h = blk(h, ctx)
-        h = self.proj_out(h)
-        return res + h.reshape(B, H, W, C).permute(0, 3, 1, 2)
+        return OF.add_nhwc_to_nchw(x, self.proj_out(h))
 
 
 class Downsample(nn.Module):

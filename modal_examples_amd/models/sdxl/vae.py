@@ -6,14 +6,17 @@ compiles exactly this module).  Channels (512,512,256,128), 3 resnets per
 level, nearest-2x upsample, mid-block single-head attention over 128² tokens.
 
 MI355X mapping: GroupNorm+SiLU → fused gfx950 kernel; convs → MIOpen;
-mid attention (1 head × 512 dim) → chunked hipBLASLt matmul+softmax (head_dim
-512 is outside the MFMA flash kernel's D∈{64,128}; one layer, ~0.5 GFLOP-ms).
+mid attention (1 head × 512 dim) → chunked hipBLASLt matmuls around one
+scaled-softmax kernel, bf16 in and out (head_dim 512 is outside the MFMA
+flash kernel's D∈{64,128}; one layer, ~0.5 GFLOP-ms); its GroupNorm writes
+[B, HW, C] itself and one transposing add returns to NCHW.
 """
 from __future__ import annotations
 
 import torch
 import torch.nn as nn
 
+from ...ops import functional as OF
 from .layers import Conv1x1, Conv3x3, GroupNormSiLU
 
 
@@ -50,16 +53,15 @@ class VAEMidAttention(nn.Module):
         self.scale = c ** -0.5
 
     def forward(self, x):
-        B, C, H, W = x.shape
-        h = self.norm(x).permute(0, 2, 3, 1).reshape(B, H * W, C)
+        h = self.norm(x, out_nhwc=True)  # [B, HW, C] straight from the kernel
         q, k, v = self.q(h), self.k(h), self.v(h)
         outs = []
         for i in range(0, q.shape[1], self.chunk):
-            s = torch.matmul(q[:, i:i + self.chunk], k.transpose(1, 2)) * self.scale
-            p = torch.softmax(s.float(), dim=-1).to(v.dtype)
-            outs.append(torch.matmul(p, v))
+            s = torch.matmul(q[:, i:i + self.chunk], k.transpose(1, 2))
+            # scale, fp32 softmax and the cast back in one pass over s
+            outs.append(torch.matmul(OF.scaled_softmax(s, self.scale), v))
         o = self.out(torch.cat(outs, dim=1))
-        return x + o.reshape(B, H, W, C).permute(0, 3, 1, 2)
+        return OF.add_nhwc_to_nchw(x, o)
 
 
 class VAEDecoder(nn.Module):

@@ -32,8 +32,17 @@ int paged_prefill_bf16(const void*, const void*, const void*, const int*,
 void groupnorm_silu_bf16(const void*, void*, float*, const float*,
                          const float*, int, int, long long, int, float, int,
                          hipStream_t);
+void groupnorm_silu_nhwc_bf16(const void*, void*, float*, const float*,
+                              const float*, int, int, long long, int, float,
+                              int, hipStream_t);
 void layernorm_bf16(const void*, void*, const float*, const float*, long long,
                     int, float, hipStream_t);
+void add_layernorm_bf16(const void*, const void*, void*, void*, const float*,
+                        const float*, long long, int, float, hipStream_t);
+void add_nhwc_to_nchw_bf16(const void*, const void*, void*, int, int,
+                           long long, hipStream_t);
+void scaled_softmax_bf16(const void*, void*, long long, int, float,
+                         hipStream_t);
 void rmsnorm_bf16(const void*, void*, const float*, long long, int, float,
                   hipStream_t);
 void cfg_euler_bf16(const void*, const void*, const void*, void*, float, float,
@@ -61,9 +70,9 @@ void cfg_euler_dev_bf16(const void*, const void*, const void*, void*,
                         const float*, const long long*, float, long long,
                         hipStream_t);
 void advance_step(long long*, hipStream_t);
-void conv3x3_bf16(const void*, const void*, const void*, const void*, void*,
-                  const float*, const float*, int, int, int, int, int, int,
-                  int, int, hipStream_t);
+void conv3x3_bf16(const void*, const void*, const void*, const void*,
+                  const void*, void*, const float*, const float*, int, int,
+                  int, int, int, int, int, int, hipStream_t);
 void gn_conv_coeffs_bf16(const void*, float*, const float*, const float*,
                          float*, float*, int, int, int, long long, int, float,
                          hipStream_t);
@@ -411,6 +420,83 @@ torch::Tensor layernorm(torch::Tensor x, torch::Tensor gamma,
   return y;
 }
 
+// a per-channel fp32 parameter vector of the fused glue ops below
+void check_f32_param(const char* op, const torch::Tensor& t, const char* name,
+                     int64_t n) {
+  TORCH_CHECK(t.is_cuda(), op, ": ", name, " must be on GPU");
+  TORCH_CHECK(t.scalar_type() == torch::kFloat, op, ": ", name,
+              " must be fp32");
+  TORCH_CHECK(t.is_contiguous() && t.dim() == 1 && t.numel() == n, op, ": ",
+              name, " must be a contiguous vector of ", n, " elements, got ",
+              t.sizes());
+}
+
+void check_same_device(const char* op, const torch::Tensor& a,
+                       const torch::Tensor& b, const char* name) {
+  TORCH_CHECK(a.device() == b.device(), op, ": ", name, " is on ", b.device(),
+              ", expected ", a.device());
+}
+
+// GroupNorm(+SiLU) of an NCHW tensor, written as [N, H*W, C] (NHWC flattened
+// over the pixels): groupnorm_silu(x).permute(0,2,3,1).reshape(N, HW, C)
+// without the transposing copy.  Everything is checked before the launch.
+torch::Tensor groupnorm_silu_nhwc(torch::Tensor x, torch::Tensor gamma,
+                                  torch::Tensor beta, int64_t groups,
+                                  double eps, bool do_silu) {
+  const char* op = "groupnorm_silu_nhwc";
+  check_bf16(x, "x");
+  TORCH_CHECK(x.dim() == 4, op, ": x must be NCHW, got ", x.dim(), " dims");
+  const int64_t N = x.size(0), C = x.size(1), HW = x.size(2) * x.size(3);
+  TORCH_CHECK(groups >= 1 && C >= 1 && C % groups == 0, op,
+              ": groups must be at least 1 and divide C, got groups=", groups,
+              " C=", C);
+  check_f32_param(op, gamma, "gamma", C);
+  check_f32_param(op, beta, "beta", C);
+  check_same_device(op, x, gamma, "gamma");
+  check_same_device(op, x, beta, "beta");
+  // grid z is the image, grid x the pixel tile; N*groups indexes the sums
+  TORCH_CHECK(N <= 65535 && HW < (1ll << 31) && C < (1ll << 22) &&
+                  N * groups < (1ll << 20),
+              op, ": too large for the kernel (N <= 65535, H*W < 2^31, "
+              "C < 2^22, N*groups < 2^20), got x ", x.sizes());
+  auto y = torch::empty({N, HW, C}, x.options());
+  auto ws = torch::zeros({N * groups * 2}, x.options().dtype(torch::kFloat32));
+  groupnorm_silu_nhwc_bf16(x.data_ptr(), y.data_ptr(), ws.data_ptr<float>(),
+                           gamma.data_ptr<float>(), beta.data_ptr<float>(),
+                           (int)N, (int)C, HW, (int)groups, (float)eps,
+                           do_silu ? 1 : 0, cur_stream());
+  return y;
+}
+
+// (x + y, LayerNorm(x + y)) over the last dimension, from one read of x, y.
+std::vector<torch::Tensor> add_layernorm(torch::Tensor x, torch::Tensor y,
+                                         torch::Tensor gamma,
+                                         torch::Tensor beta, double eps) {
+  const char* op = "add_layernorm";
+  check_bf16(x, "x");
+  check_bf16(y, "y");
+  check_same_device(op, x, y, "y");
+  TORCH_CHECK(x.dim() >= 1 && x.sizes() == y.sizes(), op,
+              ": x and y must have one shape, got ", x.sizes(), " and ",
+              y.sizes());
+  const int64_t D = x.size(-1);
+  TORCH_CHECK(D >= 8 && D % 8 == 0 && D < (1ll << 31), op,
+              ": the last dimension must be a positive multiple of 8 (rows "
+              "start on 16-byte boundaries), got ", D);
+  check_f32_param(op, gamma, "gamma", D);
+  check_f32_param(op, beta, "beta", D);
+  check_same_device(op, x, gamma, "gamma");
+  check_same_device(op, x, beta, "beta");
+  const int64_t rows = x.numel() / D;
+  TORCH_CHECK((rows + 3) / 4 < (1ll << 31), op, ": too many rows: ", rows);
+  auto s = torch::empty_like(x);
+  auto ln = torch::empty_like(x);
+  add_layernorm_bf16(x.data_ptr(), y.data_ptr(), s.data_ptr(), ln.data_ptr(),
+                     gamma.data_ptr<float>(), beta.data_ptr<float>(), rows,
+                     (int)D, (float)eps, cur_stream());
+  return {s, ln};
+}
+
 torch::Tensor rmsnorm(torch::Tensor x, torch::Tensor gamma, double eps) {
   check_bf16(x, "x");
   int D = x.size(-1);
@@ -471,6 +557,47 @@ torch::Tensor add_residual(torch::Tensor a, torch::Tensor b) {
   check_bf16(a, "a");
   auto y = torch::empty_like(a);
   add_bf16(a.data_ptr(), b.data_ptr(), y.data_ptr(), a.numel(), cur_stream());
+  return y;
+}
+
+// res [N,C,H,W] + h [N,H*W,C] -> [N,C,H,W]: the NHWC result of a
+// sequence-major section joins its NCHW residual in one pass.
+torch::Tensor add_nhwc_to_nchw(torch::Tensor res, torch::Tensor h) {
+  const char* op = "add_nhwc_to_nchw";
+  check_bf16(res, "res");
+  check_bf16(h, "h");
+  check_same_device(op, res, h, "h");
+  TORCH_CHECK(res.dim() == 4, op, ": res must be NCHW, got ", res.dim(),
+              " dims");
+  const int64_t N = res.size(0), C = res.size(1),
+                HW = res.size(2) * res.size(3);
+  TORCH_CHECK(h.dim() == 3 && h.size(0) == N && h.size(1) == HW &&
+                  h.size(2) == C,
+              op, ": h must be [N, H*W, C] = [", N, ", ", HW, ", ", C,
+              "], got ", h.sizes());
+  TORCH_CHECK(N <= 65535 && HW < (1ll << 31) && C < (1ll << 22), op,
+              ": too large for the kernel (N <= 65535, H*W < 2^31, C < 2^22), "
+              "got res ", res.sizes());
+  auto out = torch::empty_like(res);
+  add_nhwc_to_nchw_bf16(res.data_ptr(), h.data_ptr(), out.data_ptr(), (int)N,
+                        (int)C, HW, cur_stream());
+  return out;
+}
+
+// softmax((s * scale).float(), -1).to(bf16) over the last dimension.
+torch::Tensor scaled_softmax(torch::Tensor s, double scale) {
+  const char* op = "scaled_softmax";
+  check_bf16(s, "s");
+  TORCH_CHECK(s.dim() >= 1, op, ": s must have at least one dimension");
+  const int64_t V = s.size(-1);
+  TORCH_CHECK(V >= 8 && V % 8 == 0 && V < (1ll << 31), op,
+              ": the last dimension must be a positive multiple of 8, got ",
+              V);
+  const int64_t rows = s.numel() / V;
+  TORCH_CHECK(rows < (1ll << 31), op, ": too many rows: ", rows);
+  auto y = torch::empty_like(s);
+  scaled_softmax_bf16(s.data_ptr(), y.data_ptr(), rows, (int)V, (float)scale,
+                      cur_stream());
   return y;
 }
 
@@ -560,13 +687,27 @@ ConvDims check_conv(const char* op, const torch::Tensor& x,
   return d;
 }
 
+// addend [N, K] bf16 is added per (image, output channel) after the conv's
+// own bf16 rounding; it excludes a residual (no caller needs the pair).
 torch::Tensor conv3x3(torch::Tensor x, torch::Tensor wr, torch::Tensor bias,
                       c10::optional<torch::Tensor> residual, int64_t K,
-                      bool upsample) {
+                      bool upsample, c10::optional<torch::Tensor> addend) {
   const ConvDims d = check_conv("conv3x3", x, wr, bias, residual, K, upsample);
+  if (addend.has_value()) {
+    TORCH_CHECK(!residual.has_value(),
+                "conv3x3: addend and residual cannot be combined");
+    check_bf16(*addend, "addend");
+    TORCH_CHECK(addend->device() == x.device(), "conv3x3: addend is on ",
+                addend->device(), ", x on ", x.device());
+    TORCH_CHECK(addend->dim() == 2 && addend->size(0) == d.N &&
+                    addend->size(1) == K,
+                "conv3x3: addend must be [N, K] = [", d.N, ", ", K, "], got ",
+                addend->sizes());
+  }
   auto out = torch::empty({d.N, K, d.Ho, d.Wo}, x.options());
   conv3x3_bf16(x.data_ptr(), wr.data_ptr(), bias.data_ptr(),
                residual.has_value() ? residual->data_ptr() : nullptr,
+               addend.has_value() ? addend->data_ptr() : nullptr,
                out.data_ptr(), nullptr, nullptr, d.N, d.C, d.Ho, d.Wo, (int)K,
                d.C16, d.Kpad, upsample ? 1 : 0, cur_stream());
   return out;
@@ -598,7 +739,7 @@ torch::Tensor conv3x3_gn(torch::Tensor x, torch::Tensor wr, torch::Tensor bias,
   auto out = torch::empty({N, K, d.Ho, d.Wo}, x.options());
   conv3x3_bf16(x.data_ptr(), wr.data_ptr(), bias.data_ptr(),
                residual.has_value() ? residual->data_ptr() : nullptr,
-               out.data_ptr(), scale.data_ptr<float>(),
+               nullptr, out.data_ptr(), scale.data_ptr<float>(),
                shift.data_ptr<float>(), N, d.C, d.Ho, d.Wo, (int)K, C16,
                d.Kpad, upsample ? 1 : 0, cur_stream());
   return out;
@@ -877,7 +1018,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "paged KV prefill attention: ragged causal chunks over a cached "
         "prefix (K6)");
   m.def("groupnorm_silu", &groupnorm_silu);
+  m.def("groupnorm_silu_nhwc", &groupnorm_silu_nhwc,
+        "GroupNorm(+SiLU) of NCHW x, written as [N, H*W, C]");
   m.def("layernorm", &layernorm);
+  m.def("add_layernorm", &add_layernorm,
+        "(x + y, LayerNorm(x + y)) from one read of x and y");
+  m.def("add_nhwc_to_nchw", &add_nhwc_to_nchw,
+        "res [N,C,H,W] + h [N,H*W,C], tiled transpose in LDS");
+  m.def("scaled_softmax", &scaled_softmax,
+        "softmax((s * scale).float(), -1).to(bf16), bf16 in and out");
   m.def("rmsnorm", &rmsnorm);
   m.def("cfg_euler", &cfg_euler, "fused CFG + Euler step (K4)");
   m.def("silu_mul", &silu_mul);
@@ -891,7 +1040,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "per-row temperature/seed/counter/cutoff gumbel sampling (K8)");
   m.def("sampling_cutoff", &sampling_cutoff_fwd,
         "per-row top-k/top-p/min-p logit cutoff by radix select (K8)");
-  m.def("conv3x3", &conv3x3, "NCHW implicit-GEMM 3x3 conv, fused bias+res (K3)");
+  m.def("conv3x3", &conv3x3,
+        "NCHW implicit-GEMM 3x3 conv, fused bias + residual or [N,K] addend "
+        "(K3)",
+        pybind11::arg("x"), pybind11::arg("wr"), pybind11::arg("bias"),
+        pybind11::arg("residual"), pybind11::arg("K"),
+        pybind11::arg("upsample"), pybind11::arg("addend") = pybind11::none());
   m.def("conv3x3_gn", &conv3x3_gn, "GroupNorm+SiLU fused into the K3 conv");
   m.def("softmax_fwd", &softmax_fwd);
   m.def("moe_route", &moe_route,

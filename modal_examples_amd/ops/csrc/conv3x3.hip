@@ -37,6 +37,11 @@
 //    are unconditional (clamped on edge tiles) and issue 16 at a time with
 //    one wait per batch; interior tiles carry no per-element condition, edge
 //    tiles mask only the stores.
+//  - Optional per-(n, k) addend (the UNet resnets' time-embedding
+//    projection, broadcast over the pixels): out = bf16(bf16(acc + bias) +
+//    addend[n][k]) - two roundings, the arithmetic of the separate broadcast
+//    add over the conv's bf16 output that it replaces.  The block's 64 values
+//    sit in LDS beside the bias.  Not combined with a residual.
 //  - Offsets inside one image are 32-bit: the host checks C16*Hs*Ws and
 //    64*H*W below 2^31 elements (bindings.cpp check_conv).
 //
@@ -96,7 +101,7 @@ __global__ __launch_bounds__(CV_NW * WAVE, RPW == 2 ? 3 : 1)
 void conv3x3_kernel(
     const short* __restrict__ in, const short* __restrict__ wr,
     const float* __restrict__ bias, const short* __restrict__ res,
-    short* __restrict__ out, const float* __restrict__ gn_scale,
+    const short* __restrict__ addend, short* __restrict__ out, const float* __restrict__ gn_scale,
     const float* __restrict__ gn_shift, int C, int H, int W, int Hs, int Ws,
     int K, int C16, int Kpad, int npix_x, int npix, int nk) {
   constexpr int CV_ROWS = CV_NW * RPW;
@@ -108,6 +113,7 @@ void conv3x3_kernel(
   __shared__ alignas(16) short patch[PATCH_ELEMS];
   __shared__ alignas(16) short wlds[WLDS_ELEMS];
   __shared__ alignas(16) float bias_s[CV_BK];
+  __shared__ alignas(16) float addend_s[CV_BK];
 
   const int tid = threadIdx.x;
   const int w = tid / WAVE;
@@ -139,7 +145,11 @@ void conv3x3_kernel(
 
   // bias: the block's 64 values go to LDS once (index clamped to K-1; the
   // loop's first barrier orders this write before the epilogue's reads).
-  if (tid < CV_BK) bias_s[tid] = bias[min(k0 + tid, K - 1)];
+  if (tid < CV_BK) {
+    const int kc = min(k0 + tid, K - 1);
+    bias_s[tid] = bias[kc];
+    if (addend != nullptr) addend_s[tid] = bf2f(addend[(long long)n * K + kc]);
+  }
 
   // ---- staging: slot s = (row, col, c-oct); thread gathers 8 strided
   // channel values (coalesced across lanes: consecutive threads read
@@ -320,8 +330,9 @@ void conv3x3_kernel(
   // per-element condition.  Edge tiles clamp (y, x, k) for the residual
   // loads and mask the stores; interior tiles have no condition at all.
   // Offsets inside the block's (n, k0) slab of 64 planes are 32-bit.
-  auto epilogue = [&](auto res_c, auto edge_c) {
+  auto epilogue = [&](auto res_c, auto add_c, auto edge_c) {
     constexpr bool RES = decltype(res_c)::value;
+    constexpr bool ADD = decltype(add_c)::value;
     constexpr bool EDGE = decltype(edge_c)::value;
     // lane coordinates rebuilt from an opaque copy of tid: kept live across
     // the main loop they cost registers the loop has not got
@@ -355,12 +366,16 @@ void conv3x3_kernel(
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           const f32x4 b4 = *(const f32x4*)&bias_s[mf * 32 + 8 * q + 4 * hi5];
+          f32x4 a4;
+          if constexpr (ADD)
+            a4 = *(const f32x4*)&addend_s[mf * 32 + 8 * q + 4 * hi5];
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
             const int r = q * 4 + j;
             const int kl = mf * 32 + j + 8 * q + 4 * hi5;
             float v = acc[rr][mf][r] + b4[j];
             if constexpr (RES) v += bf2f((short)rv[r]);
+            if constexpr (ADD) v = bf2f(f2bf(v)) + a4[j];
             if (!EDGE || (pix_ok && kl <= kmax))
               *(short*)(outb + (po + (unsigned)kl * hw) * 2u) = f2bf(v);
           }
@@ -370,17 +385,23 @@ void conv3x3_kernel(
   };
   const bool edge =
       y0 + CV_ROWS > H || x0 + CV_COLS > W || k0 + CV_BK > K;
+  const std::true_type yes{};
+  const std::false_type no{};
   if (res != nullptr) {
-    if (edge) epilogue(std::true_type{}, std::true_type{});
-    else epilogue(std::true_type{}, std::false_type{});
+    if (edge) epilogue(yes, no, yes);
+    else epilogue(yes, no, no);
+  } else if (addend != nullptr) {
+    if (edge) epilogue(no, yes, yes);
+    else epilogue(no, yes, no);
   } else {
-    if (edge) epilogue(std::false_type{}, std::true_type{});
-    else epilogue(std::false_type{}, std::false_type{});
+    if (edge) epilogue(no, no, yes);
+    else epilogue(no, no, no);
   }
 }
 
 extern "C" void conv3x3_bf16(const void* in, const void* wrepack,
-                             const void* bias, const void* residual, void* out,
+                             const void* bias, const void* residual,
+                             const void* addend, void* out,
                              const float* gn_scale, const float* gn_shift,
                              int N, int C, int H, int W, int K, int C16,
                              int Kpad, int upsample, hipStream_t stream) {
@@ -404,7 +425,8 @@ extern "C" void conv3x3_bf16(const void* in, const void* wrepack,
 #define CVL(UPV, GNV, RPWV) \
   hipLaunchKernelGGL((conv3x3_kernel<UPV, GNV, RPWV>), grid, block, 0, \
                      stream, (const short*)in, (const short*)wrepack, \
-                     (const float*)bias, (const short*)residual, (short*)out, \
+                     (const float*)bias, (const short*)residual, \
+                     (const short*)addend, (short*)out, \
                      gn_scale, gn_shift, C, H, W, Hs, Ws, K, C16, Kpad, \
                      npix_x, npix, nk)
   if (rpw == 4) {

@@ -160,6 +160,101 @@ extern "C" void add_bf16(const void* a, const void* b, void* y, long long n,
                      (const short*)a, (const short*)b, (short*)y, n);
 }
 
+// ------------------------------------------- residual add across the layouts
+// out[n, c, p] = res[n, c, p] + h[n, p, c]: the exit of the sequence-major
+// sections of the SDXL UNet and VAE (SpatialTransformer, VAEMidAttention),
+// where an NHWC result joins its NCHW residual.  A float add rounded once.
+// One block moves a 64-pixel x 64-channel tile of h through LDS, so the h
+// read is 16-byte vectors along c and the res read / out write 16-byte
+// vectors along p; a side whose row length is no multiple of 8 moves element
+// by element, bounds-checked.  LDS image and lane mapping as in
+// gn_norm_nhwc_kernel (norms.hip): [64 p][64 c] bf16 in 33-dword rows, the
+// transposed side one dword = a channel pair per pixel, conflict-free.
+#define AT 64
+#define AT_LD (AT + 2)
+
+__global__ __launch_bounds__(256) void add_nhwc_to_nchw_kernel(
+    const short* __restrict__ R, const short* __restrict__ Hh,
+    short* __restrict__ O, int C, int HW) {
+  __shared__ alignas(16) unsigned tile[AT * AT_LD / 2];
+  const int n = blockIdx.z;
+  const int c0 = blockIdx.y * AT, p0 = blockIdx.x * AT;
+  const int lane = threadIdx.x % WAVE, wv = threadIdx.x / WAVE;
+  // NCHW side of this thread: channels (ca, ca + 1), pixels pa .. pa + 7.
+  // The residual loads go out with the h loads, ahead of the barrier.
+  const int ca = c0 + 2 * (lane % 8 + 8 * wv);
+  const int pl = (lane / 8) * 8, pa = p0 + pl;
+  short rv[2][8];
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int c = ca + h;
+    const short* rr = R + ((long long)n * C + c) * HW;
+    if (c < C && (HW % 8) == 0 && pa < HW) {
+      const bf16x8 t = *(const bf16x8*)&rr[pa];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) rv[h][j] = t[j];
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        rv[h][j] = (c < C && pa + j < HW) ? rr[pa + j] : (short)0;
+    }
+  }
+  // NHWC side: pixel pb, channels cb .. cb + 7
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int pr = threadIdx.x / 8 + 32 * i, pb = p0 + pr;
+    const int cl = (threadIdx.x % 8) * 8, cb = c0 + cl;
+    unsigned d[4] = {0u, 0u, 0u, 0u};
+    if (pb < HW && cb < C) {
+      const short* hr = Hh + ((long long)n * HW + pb) * C;
+      if ((C % 8) == 0) {
+        const i32x4 t = *(const i32x4*)&hr[cb];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) d[q] = (unsigned)t[q];
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          if (cb + j < C)
+            d[j / 2] |= (unsigned)(unsigned short)hr[cb + j] << (16 * (j & 1));
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) tile[(pr * AT_LD + cl) / 2 + q] = d[q];
+  }
+  __syncthreads();
+  bf16x8 o[2];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const unsigned t = tile[((pl + j) * AT_LD + (ca - c0)) / 2];
+    o[0][j] = f2bf(bf2f(rv[0][j]) + bf2f((short)(t & 0xffffu)));
+    o[1][j] = f2bf(bf2f(rv[1][j]) + bf2f((short)(t >> 16)));
+  }
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int c = ca + h;
+    short* orow = O + ((long long)n * C + c) * HW;
+    if (c >= C || pa >= HW) continue;
+    if ((HW % 8) == 0) {
+      *(bf16x8*)&orow[pa] = o[h];
+    } else {
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (pa + j < HW) orow[pa + j] = o[h][j];
+    }
+  }
+}
+
+// res, out: [N, C, HW]; h: [N, HW, C].  N <= 65535, HW < 2^31 (binding).
+extern "C" void add_nhwc_to_nchw_bf16(const void* res, const void* h,
+                                      void* out, int N, int C, long long HW,
+                                      hipStream_t stream) {
+  if (N == 0 || C == 0 || HW == 0) return;
+  dim3 grid((unsigned)((HW + AT - 1) / AT), (C + AT - 1) / AT, N);
+  hipLaunchKernelGGL(add_nhwc_to_nchw_kernel, grid, dim3(256), 0, stream,
+                     (const short*)res, (const short*)h, (short*)out, C,
+                     (int)HW);
+}
+
 // ---------------------------------------------------------------- RoPE
 // q/k: [B, H, S, D] bf16; cos/sin: [S, D/2] f32 host-precomputed (G13/App.B:
 // on-device trig turns this memory-bound op VALU-bound). Llama rotate-half

@@ -154,6 +154,148 @@ extern "C" void softmax_rows(const float* x, float* y, int rows, int V,
                      stream, x, y, rows, V);
 }
 
+// ------------------------------------------- scaled row softmax, bf16 -> bf16
+// softmax((s * scale).float(), -1).to(bf16) in one pass over HBM (the VAE
+// mid-attention score chunks, [16, 2048, 16384]: the four-kernel torch chain
+// moves 12.8 GB per chunk, this moves 4.3).  The product is rounded to bf16
+// first - `s * scale` is a bf16 tensor in the chain this replaces - then max,
+// exponential and sum are fp32.  One block per row; V % 8 == 0.
+//
+// Rows up to SSM_NV * 2048 columns stay in registers between the read and
+// the write; longer rows run an online (max, sum) pass and read the row a
+// second time.
+
+#define SSM_MAX_NV 8  // bf16x8 vectors per thread held in registers
+
+DEV_INLINE float ssm_block_max(float v, float* sh) {
+  v = wave_max(v);
+  const int w = threadIdx.x / WAVE;
+  if (threadIdx.x % WAVE == 0) sh[w] = v;
+  __syncthreads();
+  float r = sh[0];
+#pragma unroll
+  for (int j = 1; j < SMP_BLOCK / WAVE; ++j) r = fmaxf(r, sh[j]);
+  return r;
+}
+
+DEV_INLINE float ssm_block_sum(float v, float* sh) {
+  v = wave_sum(v);
+  const int w = threadIdx.x / WAVE;
+  if (threadIdx.x % WAVE == 0) sh[w] = v;
+  __syncthreads();
+  float r = sh[0];
+#pragma unroll
+  for (int j = 1; j < SMP_BLOCK / WAVE; ++j) r += sh[j];
+  return r;
+}
+
+// the bf16-rounded product, as the float the softmax works on
+DEV_INLINE float ssm_scaled(short s, float scale) {
+  return bf2f(f2bf(bf2f(s) * scale));
+}
+
+template <int NV>
+__global__ __launch_bounds__(SMP_BLOCK) void scaled_softmax_kernel(
+    const short* __restrict__ X, short* __restrict__ Y, int V, float scale) {
+  __shared__ float shm[SMP_BLOCK / WAVE], shs[SMP_BLOCK / WAVE];
+  const long long row = blockIdx.x;
+  const short* x = X + row * V;
+  short* y = Y + row * V;
+  const int nvec = V / 8;
+  float f[NV][8];
+  float m = -INFINITY;
+#pragma unroll
+  for (int k = 0; k < NV; ++k) {
+    const int vi = k * SMP_BLOCK + threadIdx.x;
+    if (vi < nvec) {
+      const bf16x8 v = *(const bf16x8*)&x[vi * 8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        f[k][j] = ssm_scaled(v[j], scale);
+        m = fmaxf(m, f[k][j]);
+      }
+    }
+  }
+  m = ssm_block_max(m, shm);
+  float l = 0.f;
+#pragma unroll
+  for (int k = 0; k < NV; ++k) {
+    const int vi = k * SMP_BLOCK + threadIdx.x;
+    if (vi < nvec) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        f[k][j] = __expf(f[k][j] - m);
+        l += f[k][j];
+      }
+    }
+  }
+  l = ssm_block_sum(l, shs);
+  const float inv = 1.f / l;
+#pragma unroll
+  for (int k = 0; k < NV; ++k) {
+    const int vi = k * SMP_BLOCK + threadIdx.x;
+    if (vi < nvec) {
+      bf16x8 o;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) o[j] = f2bf(f[k][j] * inv);
+      *(bf16x8*)&y[vi * 8] = o;
+    }
+  }
+}
+
+__global__ __launch_bounds__(SMP_BLOCK) void scaled_softmax_long_kernel(
+    const short* __restrict__ X, short* __restrict__ Y, int V, float scale) {
+  __shared__ float shm[SMP_BLOCK / WAVE], shs[SMP_BLOCK / WAVE];
+  const long long row = blockIdx.x;
+  const short* x = X + row * V;
+  short* y = Y + row * V;
+  const int nvec = V / 8;
+  float m = -INFINITY;
+  for (int vi = threadIdx.x; vi < nvec; vi += SMP_BLOCK) {
+    const bf16x8 v = *(const bf16x8*)&x[vi * 8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) m = fmaxf(m, ssm_scaled(v[j], scale));
+  }
+  m = ssm_block_max(m, shm);
+  float l = 0.f;
+  for (int vi = threadIdx.x; vi < nvec; vi += SMP_BLOCK) {
+    const bf16x8 v = *(const bf16x8*)&x[vi * 8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) l += __expf(ssm_scaled(v[j], scale) - m);
+  }
+  l = ssm_block_sum(l, shs);
+  const float inv = 1.f / l;
+  for (int vi = threadIdx.x; vi < nvec; vi += SMP_BLOCK) {
+    const bf16x8 v = *(const bf16x8*)&x[vi * 8];
+    bf16x8 o;
+#pragma unroll
+    for (int j = 0; j < 8; ++j)
+      o[j] = f2bf(__expf(ssm_scaled(v[j], scale) - m) * inv);
+    *(bf16x8*)&y[vi * 8] = o;
+  }
+}
+
+// x, y: [rows, V] contiguous bf16, V % 8 == 0, rows < 2^31 (checked by the
+// binding).
+extern "C" void scaled_softmax_bf16(const void* x, void* y, long long rows,
+                                    int V, float scale, hipStream_t stream) {
+  if (rows == 0 || V == 0) return;
+  const int nv = (V / 8 + SMP_BLOCK - 1) / SMP_BLOCK;
+#define SSM(NVV) \
+  hipLaunchKernelGGL(scaled_softmax_kernel<NVV>, dim3((unsigned)rows), \
+                     dim3(SMP_BLOCK), 0, stream, (const short*)x, (short*)y, \
+                     V, scale)
+  if (nv <= 1) SSM(1);
+  else if (nv <= 2) SSM(2);
+  else if (nv <= 4) SSM(4);
+  else if (nv <= SSM_MAX_NV) SSM(SSM_MAX_NV);
+  else
+    hipLaunchKernelGGL(scaled_softmax_long_kernel, dim3((unsigned)rows),
+                       dim3(SMP_BLOCK), 0, stream, (const short*)x, (short*)y,
+                       V, scale);
+#undef SSM
+}
+
 // ------------------------------------------------- per-row filtered sampling
 // Batched sampling with per-row temperature, top-k / top-p / min-p, seed and
 // counter, all read from device arrays (nothing comes back to the host).

@@ -216,12 +216,22 @@ def paged_prefill(q, k_cache, v_cache, block_table, cu_q, seq_lens,
 
 
 def groupnorm_silu(x, gamma, beta, groups: int = 32, eps: float = 1e-5,
-                   do_silu: bool = True):
+                   do_silu: bool = True, out_nhwc: bool = False):
+    """GroupNorm(+SiLU) of x [N,C,H,W].  out_nhwc=True returns the result as
+    [N, H*W, C] — `groupnorm_silu(x).permute(0, 2, 3, 1).reshape(N, H*W, C)`
+    — which the kernel writes directly (same statistics pass, an apply kernel
+    that transposes its tile in LDS), so the sequence-major sections of the
+    UNet/VAE take it without a transposing copy."""
     ext = _ext_for(x, gamma, beta)
     if ext is None:
-        return ref.groupnorm_silu_ref(x, gamma, beta, groups, eps, do_silu)
-    return ext.groupnorm_silu(x.contiguous(), gamma.float().contiguous(),
-                              beta.float().contiguous(), groups, eps, do_silu)
+        y = ref.groupnorm_silu_ref(x, gamma, beta, groups, eps, do_silu)
+        if out_nhwc:
+            N, C, H, W = x.shape
+            y = y.permute(0, 2, 3, 1).reshape(N, H * W, C)
+        return y
+    fn = ext.groupnorm_silu_nhwc if out_nhwc else ext.groupnorm_silu
+    return fn(x.contiguous(), gamma.float().contiguous(),
+              beta.float().contiguous(), groups, eps, do_silu)
 
 
 def layernorm(x, gamma, beta, eps: float = 1e-5):
@@ -230,6 +240,47 @@ def layernorm(x, gamma, beta, eps: float = 1e-5):
         return ref.layernorm_ref(x, gamma, beta, eps)
     return ext.layernorm(x.contiguous(), gamma.float().contiguous(),
                          beta.float().contiguous(), eps)
+
+
+def add_layernorm(x, y, gamma, beta, eps: float = 1e-5):
+    """(x + y, layernorm(x + y)): a residual add and the norm of the next
+    sub-layer from one read of x and y.  The sum is rounded to x's dtype and
+    the norm works on the rounded sum, so both results equal `s = x + y`
+    followed by `layernorm(s, ...)` bit for bit.  A last dimension that is
+    no multiple of 8 runs exactly those two ops."""
+    ext = _ext_for(x, y, gamma, beta)
+    if ext is None or x.shape[-1] % 8 != 0 or x.shape != y.shape \
+            or y.dtype is not x.dtype:
+        s = x + y
+        return s, layernorm(s, gamma, beta, eps)
+    s, ln = ext.add_layernorm(x.contiguous(), y.contiguous(),
+                              gamma.float().contiguous(),
+                              beta.float().contiguous(), eps)
+    return s, ln
+
+
+def add_nhwc_to_nchw(res, h):
+    """res [N,C,H,W] + h [N,H*W,C] -> [N,C,H,W], i.e.
+    `res + h.reshape(N, H, W, C).permute(0, 3, 1, 2)` as one tiled-transpose
+    kernel instead of a strided TensorIterator add."""
+    N, C, H, W = res.shape
+    ext = _ext_for(res, h)
+    if ext is None or h.dtype is not res.dtype:
+        return res + h.reshape(N, H, W, C).permute(0, 3, 1, 2)
+    return ext.add_nhwc_to_nchw(res.contiguous(), h.contiguous())
+
+
+def scaled_softmax(s, scale: float):
+    """softmax((s * scale).float(), -1).to(s.dtype) for bf16 scores: one read
+    and one write of the score matrix instead of the four-kernel chain.  The
+    product is rounded to bf16 before the fp32 softmax, as in the chain.
+    Rows must be contiguous with a multiple of 8 columns; anything else runs
+    the torch expression."""
+    ext = _ext_for(s)
+    if ext is None or s.shape[-1] % 8 != 0 or s.shape[-1] == 0 \
+            or not s.is_contiguous():
+        return torch.softmax((s * scale).float(), dim=-1).to(s.dtype)
+    return ext.scaled_softmax(s, scale)
 
 
 def rmsnorm(x, gamma, eps: float = 1e-6):
@@ -330,12 +381,23 @@ def repack_conv3x3_weight(weight: torch.Tensor) -> torch.Tensor:
 
 
 def conv3x3(x, wr, bias, K: int, residual=None, raw_weight=None,
-            upsample: bool = False):
+            upsample: bool = False, addend=None):
     """3x3 stride-1 pad-1 conv (K3). x [N,C,H,W] bf16; wr from
     repack_conv3x3_weight; bias fp32 [K]; optional fused residual add;
     upsample=True fuses a nearest-2x upsample of x into the conv read.
+    addend [N,K] (x's dtype) is added per (image, output channel) to the
+    rounded conv output — `conv3x3(x, ...) + addend[:, :, None, None]` in the
+    kernel's epilogue; it cannot be combined with residual.
     raw_weight [K,C,3,3] drives the CPU/autograd reference path."""
-    ext = _ext_for(x, raw_weight if raw_weight is not None else x)
+    if addend is not None and residual is not None:
+        raise ValueError("conv3x3: addend and residual cannot be combined")
+    ext = _ext_for(x, raw_weight if raw_weight is not None else x, addend)
+    if ext is not None and addend is not None:
+        return ext.conv3x3(x.contiguous(), wr, bias, None, K, upsample,
+                           addend.contiguous())
+    if addend is not None:
+        return conv3x3(x, wr, bias, K, raw_weight=raw_weight,
+                       upsample=upsample) + addend[:, :, None, None]
     if ext is None:
         assert raw_weight is not None, "reference conv path needs raw_weight"
         xin = x

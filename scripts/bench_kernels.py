@@ -239,6 +239,101 @@ def bench_memory_ops(results):
         "pct_hbm": round(100 * gb / dt / HBM_CEIL_GBS, 1)}
 
 
+def bench_sdxl_glue(results):
+    """The fused glue ops of the SDXL step at their workload shapes, each
+    timed in alternating windows beside the torch chain it replaced in the
+    models.  GB counts the bytes the fused op has to move (inputs read once,
+    outputs written once), for both columns, so chain_TBps is the chain's
+    useful rate, not its traffic."""
+    bf = dict(device="cuda", dtype=torch.bfloat16)
+
+    def graphed(fn, reps=16):
+        """Calls under 0.2 ms are bound by the host's launches when issued
+        one by one; those are timed as `reps` calls replayed from one
+        captured graph, which is also how the denoise step runs them."""
+        fn()
+        torch.cuda.synchronize()
+        if timeit(fn, iters=5, warmup=1) >= 2e-4:
+            return fn, 1
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            for _ in range(reps):
+                fn()
+        return g.replay, reps
+
+    def record(name, fused, chain, gb):
+        (fused, rf), (chain, rc) = graphed(fused), graphed(chain)
+        tf, tc = _alternate([fused, chain])
+        tf, tc = tf / rf, tc / rc
+        r = {"fused_ms": round(tf * 1e3, 4), "chain_ms": round(tc * 1e3, 4),
+             "speedup": round(tc / tf, 2),
+             "fused_TBps": round(gb / tf / 1e3, 2),
+             "chain_TBps": round(gb / tc / 1e3, 2),
+             "fused_pct_hbm": round(100 * gb / tf / HBM_CEIL_GBS, 1)}
+        results[name] = r
+        print(name, json.dumps(r), flush=True)
+
+    s = torch.randn(16, 2048, 16384, **bf)
+    scale = 512 ** -0.5
+    record("scaled_softmax/16x2048x16384",
+           lambda: F.scaled_softmax(s, scale),
+           lambda: torch.softmax((s * scale).float(), -1).to(torch.bfloat16),
+           2 * s.numel() * 2 / 1e9)
+    del s
+
+    for N, C, H in ((16, 640, 64), (16, 1280, 32), (16, 512, 128)):
+        x = torch.randn(N, C, H, H, **bf)
+        g = torch.randn(C, device="cuda")
+        b = torch.randn(C, device="cuda")
+        # statistics pass reads x, apply pass reads x and writes y.  The
+        # chain's reshape is a view; the transposing copy ran inside the
+        # Linear that followed, hence .contiguous() here
+        record(f"gn_nhwc/{N}x{C}x{H}x{H}",
+               lambda: F.groupnorm_silu(x, g, b, 32, do_silu=False,
+                                        out_nhwc=True),
+               lambda: F.groupnorm_silu(x, g, b, 32, do_silu=False)
+               .permute(0, 2, 3, 1).reshape(N, H * H, C).contiguous(),
+               3 * x.numel() * 2 / 1e9)
+        h = torch.randn(N, H * H, C, **bf)
+        record(f"add_nhwc_to_nchw/{N}x{C}x{H}x{H}",
+               lambda: F.add_nhwc_to_nchw(x, h),
+               lambda: x + h.reshape(N, H, H, C).permute(0, 3, 1, 2),
+               3 * x.numel() * 2 / 1e9)
+
+    N, C, K, H = 16, 320, 320, 128
+    x = torch.randn(N, C, H, H, **bf)
+    w = torch.randn(K, C, 3, 3, **bf) / (3 * C ** 0.5)
+    wr = F.repack_conv3x3_weight(w)
+    bias = torch.randn(K, device="cuda")
+    t = torch.randn(N, K, **bf)
+    tf, tc, tp = _alternate([
+        lambda: F.conv3x3(x, wr, bias, K, raw_weight=w, addend=t),
+        lambda: F.conv3x3(x, wr, bias, K, raw_weight=w) + t[:, :, None, None],
+        lambda: F.conv3x3(x, wr, bias, K, raw_weight=w)])
+    flops = 2.0 * N * K * C * 9 * H * H
+    r = {"fused_ms": round(tf * 1e3, 4), "chain_ms": round(tc * 1e3, 4),
+         "conv_alone_ms": round(tp * 1e3, 4), "speedup": round(tc / tf, 2),
+         "fused_TF": round(flops / tf / 1e12, 1),
+         "conv_alone_TF": round(flops / tp / 1e12, 1)}
+    results[f"conv3x3_addend/{N}x{C}to{K}at{H}"] = r
+    print(f"conv3x3_addend/{N}x{C}to{K}at{H}", json.dumps(r), flush=True)
+    del x, w, wr
+
+    for rows, D in ((65536, 640), (16384, 1280)):
+        a = torch.randn(rows, D, **bf)
+        c = torch.randn(rows, D, **bf)
+        g = torch.randn(D, device="cuda")
+        b = torch.randn(D, device="cuda")
+
+        def chain():
+            y = a + c
+            return y, F.layernorm(y, g, b)
+
+        record(f"add_layernorm/{rows}x{D}",
+               lambda: F.add_layernorm(a, c, g, b), chain,
+               4 * a.numel() * 2 / 1e9)
+
+
 def bench_gemm_reference(results):
     """hipBLASLt via torch for context."""
     for n in (4096, 8192):
@@ -256,14 +351,15 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--only", default="",
                     help="comma-separated groups: attention, attention_bwd, "
-                         "decode, paged_prefill, memory_ops, gemm_reference "
-                         "(default: all)")
+                         "decode, paged_prefill, memory_ops, sdxl_glue, "
+                         "gemm_reference (default: all)")
     args = ap.parse_args()
     assert torch.cuda.is_available()
     groups = {"attention": bench_attention,
               "attention_bwd": bench_attention_bwd,
               "decode": bench_decode, "paged_prefill": bench_paged_prefill,
               "memory_ops": bench_memory_ops,
+              "sdxl_glue": bench_sdxl_glue,
               "gemm_reference": bench_gemm_reference}
     only = [g for g in args.only.split(",") if g] or list(groups)
     results = {}
