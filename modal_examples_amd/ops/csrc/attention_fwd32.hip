@@ -10,8 +10,8 @@
 //   QK^T is computed TRANSPOSED with mfma_f32_32x32x16_bf16:
 //     S^T = K · Q^T  →  each lane holds 16 of the 32 kv-scores for ONE query
 //     (C layout col = q = lane&31); row-softmax becomes 15 in-register ops +
-//     ONE shfl_xor(32) to combine with the partner lane.  Rescale factors are
-//     lane-local (no broadcast).
+//     ONE exchange with the partner lane (lane_pair, no LDS).  Rescale
+//     factors are lane-local (no broadcast).
 //   P converts to bf16 B-fragments IN REGISTERS (c8_to_bfrag) — P never
 //     touches LDS.
 //   PV: O^T = V^T · P^T, V^T fragments by hardware transpose reads (tr_frag)
@@ -30,12 +30,13 @@
 // DEFER: defer-max rescale skipping (HK THR=8) — keep the old running max
 // while per-block growth <= 8, so P = exp(s - m_old) <= e^8 (f32 acc safe)
 // and the O-wide rescale is skipped entirely.
-// The D=64 causal instance sits at the 3-waves/SIMD register edge (168); the
-// waves-per-SIMD request keeps it there now that m_run outlives the loop for
-// the LSE.  1 is the launch-bounds default and changes nothing elsewhere.
+// Every instance asks for its occupancy floor (3 waves/SIMD at D=64, 2 at
+// D=128).  Without the request the compiler budgets 512 registers, parks the
+// accumulators in AGPRs and copies O out and back on every tile (64
+// v_accvgpr moves per tile at D=64); with it every MFMA takes its VGPR form.
 template <int D, bool CAUSAL, int KVB, bool DEFER>
 __global__ __launch_bounds__(FA32_NWAVES * WAVE)
-__attribute__((amdgpu_waves_per_eu((D == 64 && CAUSAL) ? 3 : 1)))
+__attribute__((amdgpu_waves_per_eu(D == 64 ? 3 : 2)))
 void fa32_kernel(
     const short* __restrict__ Q, const short* __restrict__ K,
     const short* __restrict__ V, short* __restrict__ O,
@@ -67,6 +68,7 @@ void fa32_kernel(
   const long long ooff = b * st.o.b + h * st.o.h;
   const int q0 = qblk * QBLK + w * 32;
   const int my_q = q0 + l31;  // this lane's query row
+  const int q0w = __builtin_amdgcn_readfirstlane(q0);  // q0, known uniform
   const int causal_off = Sk - Sq;
 
   // Q^T B-fragments: qreg[c][j] = Q[my_q][c*16 + hi5*8 + j], held in
@@ -120,36 +122,70 @@ void fa32_kernel(
     for (int f = 0; f < KF; ++f)
 #pragma unroll
       for (int r = 0; r < 16; ++r) s[f][r] = 0.f;
+    // Reads run ahead of the MFMAs: all DCH row reads of a 32-key fragment
+    // go out together into registers of their own, and while its MFMAs run
+    // the next fragment's reads (after the last one, the first V^T reads,
+    // whose tile has been in LDS since the barrier) are already in flight.
+    // LDS returns in order, so each MFMA waits on a counted lgkmcnt.  The
+    // scheduling fences keep that issue order; one priority pair per cluster.
+    // A = K[kv][d]: lane holds K[f*32 + l31][c*16 + hi5*8 + j]
+    bf16x8 kf[KF][DCH];
+    bf16x8 vf[2][DT];
+#pragma unroll
+    for (int c = 0; c < DCH; ++c)
+      kf[0][c] = row_frag<KROW>(&Ks[0][0], l31, hi5, c);
 #pragma unroll
     for (int f = 0; f < KF; ++f) {
+      if (f + 1 < KF) {
 #pragma unroll
-      for (int c = 0; c < DCH; ++c) {
-        // A = K[kv][d]: lane holds K[f*32 + l31][c*16 + hi5*8 + j]
-        bf16x8 kfrag = row_frag<KROW>(&Ks[0][0], f * 32 + l31, hi5, c);
-        __builtin_amdgcn_s_setprio(1);
-        s[f] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfrag, qreg[c], s[f], 0,
-                                                       0, 0);
-        __builtin_amdgcn_s_setprio(0);
+        for (int c = 0; c < DCH; ++c)
+          kf[f + 1][c] = row_frag<KROW>(&Ks[0][0], (f + 1) * 32 + l31, hi5, c);
+      } else {
+#pragma unroll
+        for (int dt = 0; dt < DT; ++dt)
+          vf[0][dt] = tr_frag<KROW>(&Vs[0][0], l, hi5, 0, dt);
       }
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int c = 0; c < DCH; ++c)
+        s[f] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[f][c], qreg[c], s[f],
+                                                       0, 0, 0);
+      __builtin_amdgcn_s_setprio(0);
+      __builtin_amdgcn_sched_barrier(0);
     }
 
     // ---- mask + lane-local online softmax (this lane owns query my_q) ----
-    bool full = (kb * KVB + KVB <= Sk) &&
-                (!CAUSAL || kb * KVB + KVB - 1 <= my_q + causal_off);
+    // A tile is interior when every key of it exists and, under the causal
+    // mask, is visible to the wave's FIRST row (so to all 32).  The test is
+    // wave-uniform: interior tiles branch past the per-score compares and
+    // selects.  An edge tile masks per element; a lane whose own row sees the
+    // whole tile gets the same s * scale there.
+    const bool full = (kb * KVB + KVB <= Sk) &&
+                      (!CAUSAL || kb * KVB + KVB - 1 <= q0w + causal_off);
+    if (full) {
 #pragma unroll
-    for (int f = 0; f < KF; ++f)
+      for (int f = 0; f < KF; ++f)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        int kvp = kb * KVB + f * 32 + c_row(r, hi5);
-        bool dead = !full && ((kvp >= Sk) || (CAUSAL && kvp > my_q + causal_off));
-        s[f][r] = dead ? -1e30f : s[f][r] * scale;
-      }
+        for (int r = 0; r < 16; ++r) s[f][r] *= scale;
+    } else {
+#pragma unroll
+      for (int f = 0; f < KF; ++f)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          int kvp = kb * KVB + f * 32 + c_row(r, hi5);
+          bool dead = (kvp >= Sk) || (CAUSAL && kvp > my_q + causal_off);
+          s[f][r] = dead ? -1e30f : s[f][r] * scale;
+        }
+    }
     float smax = s[0][0];
 #pragma unroll
     for (int f = 0; f < KF; ++f)
 #pragma unroll
       for (int r = 0; r < 16; ++r) smax = fmaxf(smax, s[f][r]);
-    smax = fmaxf(smax, __shfl_xor(smax, 32, WAVE));  // partner combine
+    float pa, pb;
+    lane_pair(smax, pa, pb);  // partner combine, in registers
+    smax = fmaxf(pa, pb);
     if (!DEFER || kb == 0 ||
         __ballot(smax > m_run + 8.f) != 0ull) {
       float m_new = fmaxf(m_run, smax);
@@ -171,7 +207,8 @@ void fa32_kernel(
         s[f][r] = __expf(s[f][r] - m_run);
         psum += s[f][r];
       }
-    psum += __shfl_xor(psum, 32, WAVE);
+    lane_pair(psum, pa, pb);
+    psum = pa + pb;
     l_run = (kb == 0) ? psum : l_run + psum;
 
     // ---- P → bf16 B-fragments in registers, one per 16-kv chunk ----
@@ -181,16 +218,22 @@ void fa32_kernel(
       pfrag[c] = c8_to_bfrag((const float*)&s[c >> 1] + (c & 1) * 8);
 
     // ---- O^T += V^T · P^T (V^T via hardware transpose reads) ----
+    // chunk c + 1 is read while chunk c multiplies; chunk 0 came in above
 #pragma unroll
     for (int c = 0; c < 2 * KF; ++c) {
+      if (c + 1 < 2 * KF) {
 #pragma unroll
-      for (int dt = 0; dt < DT; ++dt) {
-        bf16x8 vfrag = tr_frag<KROW>(&Vs[0][0], l, hi5, c, dt);
-        __builtin_amdgcn_s_setprio(1);
-        acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vfrag, pfrag[c],
-                                                          acc[dt], 0, 0, 0);
-        __builtin_amdgcn_s_setprio(0);
+        for (int dt = 0; dt < DT; ++dt)
+          vf[(c + 1) & 1][dt] = tr_frag<KROW>(&Vs[0][0], l, hi5, c + 1, dt);
       }
+      __builtin_amdgcn_sched_barrier(0);
+      __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+      for (int dt = 0; dt < DT; ++dt)
+        acc[dt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(
+            vf[c & 1][dt], pfrag[c], acc[dt], 0, 0, 0);
+      __builtin_amdgcn_s_setprio(0);
+      __builtin_amdgcn_sched_barrier(0);
     }
   }
 

@@ -102,6 +102,19 @@ DEV_INLINE bf16x8 c8_to_bfrag(const float* sv) {
   return u.v;
 }
 
+// Both values of a lane pair (lane, lane^32), in registers: lo is the value
+// of the pair's lane below 32, hi the one above, the same on both lanes.
+// One permlane32_swap of x with itself (semantics above) instead of a
+// ds_bpermute round trip and its full LDS wait.  The results go through
+// plain ints: __builtin_bit_cast applied to r[1] itself reads r[0].
+DEV_INLINE void lane_pair(float x, float& lo, float& hi) {
+  int xi = __builtin_bit_cast(int, x);
+  i32x2 r = __builtin_amdgcn_permlane32_swap(xi, xi, false, false);
+  int r0 = r[0], r1 = r[1];
+  lo = __builtin_bit_cast(float, r0);
+  hi = __builtin_bit_cast(float, r1);
+}
+
 // Two-tile staging, global -> registers -> swizzled LDS, split so the loads
 // of the next block issue before this block computes.  a/b point at row 0 of
 // the (batch, head) plane, *_rs are their row strides in elements; tile rows
