@@ -399,3 +399,43 @@ def moe_ffn_ref(x, gate_up, down, weights, idx):
         h = torch.nn.functional.silu(gu[:, :F]) * gu[:, F:]
         out = out + coef[:, e:e + 1] * (h @ _wide(down[e]).T)
     return out.to(x.dtype)
+
+
+def moe_ffn_bound_ref(x, gate_up, down, weights, idx, bf16_points=False):
+    """(want, tol) in fp64 for a bf16 implementation of moe_ffn_ref that
+    rounds to bf16 exactly twice, at h = silu(gate) * up and at the output.
+
+      want      moe_ffn_ref in fp64 on the inputs as given
+      A[t, c]   sum_j w[t,j] * sum_f |h_e[t,f]| * |down_e[c,f]|, e = idx[t,j]:
+                the absolute-value propagation of h through the down
+                projection
+      tol       2 * 2^-9 * (A + |want|)
+
+    Rounding to bf16 (8 significant bits) moves a value by at most 2^-8 of
+    itself and by 2^-9 or less for most of a binade.  2^-8 * A is therefore
+    what rounding every h can move an output by if all of them err fully
+    and in the worst direction, and 2^-8 * |want| what rounding the output
+    can: tol is the worst case of the two roundings, which independent
+    roundings over ffn_dim terms stay far below.  That slack is what covers
+    fp32 accumulation (about K * 2^-24 of A) and a fast exponential.
+
+    bf16_points=True rounds h and the output to bf16 inside the same fp64
+    pipeline and returns that output in place of `want`: the yardstick that
+    shows how much of tol a correct implementation uses."""
+    E, F = gate_up.shape[0], down.shape[2]
+    xw, ww = x.double(), weights.double()
+    coef = torch.zeros(x.shape[0], E, dtype=torch.float64)
+    coef = coef.scatter_add(1, idx.long(), ww)
+    out, A = torch.zeros_like(xw), torch.zeros_like(xw)
+    for e in range(E):
+        gu = xw @ gate_up[e].double().T
+        h = torch.nn.functional.silu(gu[:, :F]) * gu[:, F:]
+        if bf16_points:
+            h = h.to(torch.bfloat16).double()
+        de = down[e].double()
+        out = out + coef[:, e:e + 1] * (h @ de.T)
+        A = A + coef[:, e:e + 1].abs() * (h.abs() @ de.abs().T)
+    tol = 2.0 * 2.0 ** -9 * (A + out.abs())
+    if bf16_points:
+        out = out.to(torch.bfloat16).double()
+    return out, tol
