@@ -27,7 +27,8 @@ from typing import Dict, List, Optional
 import torch
 
 from ...ops import functional as OF
-from .model import LlamaConfig, LlamaModel, MoEFFN
+from .model import (WEIGHT_DTYPES, LlamaConfig, LlamaModel, MoEFFN,
+                    quantize_llama_, quantize_llama_state)
 
 BLOCK = 16
 
@@ -79,7 +80,8 @@ class LlamaEngine:
                  prefix_cache: bool = False,
                  gpu_mem_util: float = 0.6,
                  prefill_attn: str = "decode",
-                 moe_impl: Optional[str] = None):
+                 moe_impl: Optional[str] = None,
+                 weight_dtype: str = "bf16"):
         """tp: optional parallel.tp.TPGroup — head-sharded tensor parallelism
         (vllm_inference.py:180 --tensor-parallel-size role).  Every rank runs
         the same engine loop on identical requests; the KV cache holds only
@@ -122,6 +124,21 @@ class LlamaEngine:
         decodes eagerly whatever use_graph says; "fused" captures and
         replays like a dense model.  Every other lane calls the same FFN.
 
+        weight_dtype: "bf16" (default) or "int4".  "int4" holds qkv, o_proj,
+        gate_up and down of every block as 4-bit weights with one bf16 scale
+        per 128 inputs (ops.quantize_w4; model.QuantLinear): 0.52 bytes per
+        weight instead of 2.  Decode batches run them on the
+        csrc/linear_w4.hip kernel, inside the decode graph like the bf16
+        model; prefill-sized batches dequantize into a scratch weight and
+        use the ordinary GEMM.  Embedding, norms and lm_head stay in
+        `dtype`.  With init_weights=True the initialised weights are
+        quantized in place before the KV pool is sized, so the pool gets
+        the freed memory; with init_weights=False the model is built with
+        empty packed buffers for load_state_dict(assign=True).  Under tp the
+        shards are quantized, and a shard whose input width is no multiple
+        of 128 raises.  MoE configs raise ValueError (int4 experts are not
+        implemented).
+
         gpu_mem_util: fraction of free HBM the KV pool claims when
         kv_blocks is unset (--gpu-memory-utilization / --mem-fraction-static
         role, lfm_snapshot.py:316 / deepseek_v4_flash.py:255)."""
@@ -131,6 +148,14 @@ class LlamaEngine:
         if self.cfg.moe_impl not in MoEFFN.IMPLS:
             raise ValueError(f"moe_impl must be one of {MoEFFN.IMPLS}, got "
                              f"{self.cfg.moe_impl!r}")
+        if weight_dtype not in WEIGHT_DTYPES:
+            raise ValueError(f"weight_dtype must be one of {WEIGHT_DTYPES}, "
+                             f"got {weight_dtype!r}")
+        if weight_dtype == "int4" and self.cfg.n_experts > 0:
+            raise ValueError("weight_dtype='int4' does not cover MoE "
+                             "experts; use weight_dtype='bf16' for an MoE "
+                             "config")
+        self.weight_dtype = weight_dtype
         self.tp = tp
         self.spec_tokens = spec_tokens
         self.spec_proposed = 0   # drafts offered
@@ -170,6 +195,11 @@ class LlamaEngine:
         if init_weights:
             with torch.device(self.device):
                 self.model = LlamaModel(self.cfg, tp=tp).to(self.device, dtype)
+            if weight_dtype == "int4":
+                quantize_llama_(self.model)
+                if self.device.type == "cuda":
+                    # hand the bf16 projections back before the pool is sized
+                    torch.cuda.empty_cache()
         else:
             # cold-restore path: build on meta (no init compute) directly in
             # the target dtype so to_empty materializes ONCE with no cast;
@@ -179,7 +209,8 @@ class LlamaEngine:
             try:
                 torch.set_default_dtype(dtype)
                 with torch.device("meta"):
-                    self.model = LlamaModel(self.cfg, tp=tp)
+                    self.model = LlamaModel(self.cfg, tp=tp,
+                                            weight_dtype=weight_dtype)
             finally:
                 torch.set_default_dtype(prev)
             self.model = self.model.to_empty(device=self.device)
@@ -238,7 +269,8 @@ class LlamaEngine:
 
     def save_safetensors(self, path: str) -> int:
         """Bake the weights for `from_safetensors` (the snapshot-build step;
-        reference role: sglang_snapshot.py:176-218 warm/sleep/wake)."""
+        reference role: sglang_snapshot.py:176-218 warm/sleep/wake).  An
+        int4 engine writes its packed `qweight` / `scales` tensors."""
         from ...gpu import fastload
 
         return fastload.save_file(dict(self.model.state_dict()), path)
@@ -250,10 +282,29 @@ class LlamaEngine:
         allocation (the hipMalloc long pole) runs on a thread WHILE the
         weight file streams through pinned staging (gpu/fastload.py), then
         the blob views are assigned as parameters.  Measured: 16 GB Llama-8B
-        end-to-end boot p50 6.4 s, best 2.9 s (profiles/final_cold_llama4)."""
+        end-to-end boot p50 6.4 s, best 2.9 s (profiles/final_cold_llama4).
+
+        Both checkpoint kinds load.  A file written by an int4 engine boots
+        an int4 engine directly (weight_dtype defaults to what the file
+        holds; asking for "bf16" raises, and so does tp.world > 1, whose
+        shards would cut through packed words).  A bf16 file with
+        weight_dtype="int4" is sharded first, if tp is set, and then
+        quantized on the device."""
         import threading
 
         from ...gpu import fastload
+
+        header, _, _ = fastload._parse(path)
+        packed = any(k.endswith(".qweight") for k in header)
+        kw.setdefault("weight_dtype", "int4" if packed else "bf16")
+        if packed and kw["weight_dtype"] != "int4":
+            raise ValueError(f"{path} holds int4 weights; it cannot boot a "
+                             f"weight_dtype={kw['weight_dtype']!r} engine")
+        tp = kw.get("tp")
+        if packed and tp is not None and tp.world > 1:
+            raise ValueError("loading an int4 checkpoint under tensor "
+                             "parallelism is not supported: boot the bf16 "
+                             "checkpoint with weight_dtype='int4' instead")
 
         box: dict = {}
 
@@ -277,6 +328,8 @@ class LlamaEngine:
 
             sd = shard_llama_state(sd, eng.cfg, eng.tp.rank, eng.tp.world)
             sd = {k: v.contiguous() for k, v in sd.items()}
+        if eng.weight_dtype == "int4" and not packed:
+            sd = quantize_llama_state(sd)
         eng.model.load_state_dict(sd, assign=True)
         return eng
 

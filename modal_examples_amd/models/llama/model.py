@@ -54,8 +54,117 @@ class LlamaConfig:
                            rope_base=10000.0, max_seq=512, n_experts=4)
 
 
+WEIGHT_DTYPES = ("bf16", "int4")
+
+
+class QuantLinear(nn.Module):
+    """Bias-free linear layer over int4 weights (ops.quantize_w4): buffers
+    `qweight` int32 [out, in/8] and `scales` bf16 [out, in/128].
+
+    Two lanes.  Up to M_KERNEL rows (decode) the forward is ops.linear_w4:
+    on the GPU the csrc/linear_w4.hip kernel, which applies each group's
+    scale to its fp32 partial sum and never rounds a dequantized weight.
+    Above that (prefill) the weight is dequantized into a scratch tensor of
+    the activation dtype and goes through the ordinary GEMM; in bf16 that
+    rounds every w_hat = scale * q to bf16, so the two lanes differ by that
+    rounding (in fp32 they are the same product).  On the CPU, in fp32 or
+    under autograd, both lanes are the reference composition."""
+
+    # rows up to which the kernel lane is taken.  Measured
+    # (profiles/linear_w4.txt, second table): at 1024 rows the kernel beats
+    # the dequantize lane on all four Llama-3-8B projections (188 / 255,
+    # 135 / 171, 765 / 1214, 395 / 665 us), at 2048 rows it loses on all
+    # four (376 / 280, 267 / 193, 1518 / 1361, 789 / 731 us).  1024 is the
+    # largest measured count on the kernel's side of the crossover.
+    M_KERNEL = 1024
+
+    def __init__(self, in_features: int, out_features: int, device=None):
+        super().__init__()
+        if in_features % 128 != 0 or in_features < 128:
+            raise ValueError(f"QuantLinear: in_features={in_features} must "
+                             f"be a multiple of the int4 group size 128")
+        if out_features % 64 != 0 or out_features < 64:
+            raise ValueError(f"QuantLinear: out_features={out_features} "
+                             f"must be a multiple of 64")
+        self.in_features, self.out_features = in_features, out_features
+        self.register_buffer("qweight", torch.zeros(
+            out_features, in_features // 8, dtype=torch.int32, device=device))
+        self.register_buffer("scales", torch.ones(
+            out_features, in_features // 128, dtype=torch.bfloat16,
+            device=device))
+
+    @classmethod
+    def from_linear(cls, lin: nn.Linear) -> "QuantLinear":
+        if lin.bias is not None:
+            raise ValueError("QuantLinear has no bias")
+        w = lin.weight.detach()
+        if w.dtype not in (torch.bfloat16, torch.float32):
+            w = w.float()
+        m = cls(lin.in_features, lin.out_features, device="meta")
+        q, s = OF.quantize_w4(w.contiguous())
+        m.qweight, m.scales = q, s
+        return m
+
+    def _apply(self, fn, recurse=True):
+        # module.to(dtype) casts every floating buffer; the scales are bf16
+        # by format (a round trip through a wider type loses nothing)
+        super()._apply(fn, recurse)
+        if self.scales.dtype is not torch.bfloat16:
+            self.scales = self.scales.to(torch.bfloat16)
+        return self
+
+    def forward(self, x):
+        rows = x.numel() // self.in_features
+        if rows <= self.M_KERNEL:
+            return OF.linear_w4(x, self.qweight, self.scales)
+        w = OF.dequantize_w4(self.qweight, self.scales).to(x.dtype)
+        return nn.functional.linear(x, w)
+
+    def extra_repr(self):
+        return (f"in_features={self.in_features}, "
+                f"out_features={self.out_features}, int4 g128")
+
+
+QUANT_PROJECTIONS = ("qkv", "o_proj", "gate_up", "down")
+
+
+def quantize_llama_(model: "LlamaModel") -> "LlamaModel":
+    """Replace qkv, o_proj, gate_up and down of every block by QuantLinear
+    modules quantized from the current weights, one projection at a time so
+    the bf16 copy of each is released as it goes.  Embedding, norms and
+    lm_head stay as they are."""
+    for blk in model.blocks:
+        if blk.moe is not None:
+            raise ValueError("int4 weights do not cover MoE experts")
+        for name in QUANT_PROJECTIONS:
+            lin = getattr(blk, name)
+            if isinstance(lin, nn.Linear):
+                setattr(blk, name, QuantLinear.from_linear(lin))
+    model.weight_dtype = "int4"
+    return model
+
+
+def quantize_llama_state(state: dict) -> dict:
+    """A bf16 state dict of a dense LlamaModel (or of one TP shard) with the
+    four block projections replaced by their `qweight` / `scales` pair."""
+    out = {}
+    for k, v in state.items():
+        parts = k.split(".")
+        if (len(parts) == 4 and parts[0] == "blocks"
+                and parts[2] in QUANT_PROJECTIONS and parts[3] == "weight"):
+            if v.dtype not in (torch.bfloat16, torch.float32):
+                v = v.float()
+            q, s = OF.quantize_w4(v.contiguous())
+            out[k[:-len("weight")] + "qweight"] = q
+            out[k[:-len("weight")] + "scales"] = s
+        else:
+            out[k] = v
+    return out
+
+
 class LlamaBlock(nn.Module):
-    def __init__(self, cfg: LlamaConfig, tp_world: int = 1):
+    def __init__(self, cfg: LlamaConfig, tp_world: int = 1,
+                 weight_dtype: str = "bf16"):
         """tp_world>1: Megatron head-sharded block (the --tensor-parallel-size
         role of vllm_inference.py:180 / trtllm tensor_parallel_size).  qkv and
         gate_up are column-sharded (this rank's q/kv-head and gate/up slices,
@@ -68,9 +177,23 @@ class LlamaBlock(nn.Module):
             f"tp={tp_world} must divide heads {cfg.n_heads}/{cfg.n_kv_heads}" \
             f" and ffn {cfg.ffn_dim}"
         self.nq, self.nkv = cfg.n_heads // tp_world, cfg.n_kv_heads // tp_world
+        if weight_dtype not in WEIGHT_DTYPES:
+            raise ValueError(f"weight_dtype must be one of {WEIGHT_DTYPES}, "
+                             f"got {weight_dtype!r}")
+        if weight_dtype == "int4":
+            # built with buffers of the right shape (meta-device boot);
+            # a shard whose K is no multiple of 128 raises here
+            if cfg.n_experts > 0:
+                raise ValueError("weight_dtype='int4' does not cover MoE "
+                                 "experts")
+
+            def linear(i, o, bias=False):
+                return QuantLinear(i, o)
+        else:
+            linear = nn.Linear
         self.attn_norm = RMSNormK(d, cfg.norm_eps)
-        self.qkv = nn.Linear(d, (self.nq + 2 * self.nkv) * hd, bias=False)
-        self.o_proj = nn.Linear(self.nq * hd, d, bias=False)
+        self.qkv = linear(d, (self.nq + 2 * self.nkv) * hd, bias=False)
+        self.o_proj = linear(self.nq * hd, d, bias=False)
         self.ffn_norm = RMSNormK(d, cfg.norm_eps)
         if cfg.n_experts > 0:
             assert tp_world == 1, "MoE + TP not supported (EP is a non-goal)"
@@ -79,9 +202,8 @@ class LlamaBlock(nn.Module):
             self.gate_up = self.down = None
         else:
             self.moe = None
-            self.gate_up = nn.Linear(d, 2 * cfg.ffn_dim // tp_world,
-                                     bias=False)
-            self.down = nn.Linear(cfg.ffn_dim // tp_world, d, bias=False)
+            self.gate_up = linear(d, 2 * cfg.ffn_dim // tp_world, bias=False)
+            self.down = linear(cfg.ffn_dim // tp_world, d, bias=False)
         self.hd = hd
         self.ffn_dim = cfg.ffn_dim // tp_world
 
@@ -104,18 +226,25 @@ class LlamaBlock(nn.Module):
 
 
 class LlamaModel(nn.Module):
-    def __init__(self, cfg: LlamaConfig, tp=None):
+    def __init__(self, cfg: LlamaConfig, tp=None, weight_dtype: str = "bf16"):
         """tp: optional parallel.tp.TPGroup — shards every block across the
         group (embed/norms/lm_head replicated; activations stay replicated,
         so logits are identical on every rank and sampling needs no extra
-        broadcast)."""
+        broadcast).
+
+        weight_dtype="int4" builds qkv, o_proj, gate_up and down of every
+        block as QuantLinear modules with empty buffers (for loading a
+        quantized state); `quantize_llama_` converts an initialised bf16
+        model in place."""
         super().__init__()
         self.cfg = cfg
+        self.weight_dtype = weight_dtype
         self.tp = tp if (tp is not None and tp.world > 1) else None
         w = self.tp.world if self.tp else 1
         self.embed = nn.Embedding(cfg.vocab_size, cfg.dim)
         self.blocks = nn.ModuleList(
-            [LlamaBlock(cfg, tp_world=w) for _ in range(cfg.n_layers)])
+            [LlamaBlock(cfg, tp_world=w, weight_dtype=weight_dtype)
+             for _ in range(cfg.n_layers)])
         self.norm = RMSNormK(cfg.dim, cfg.norm_eps)
         self.lm_head = nn.Linear(cfg.dim, cfg.vocab_size, bias=False)
         # NOT buffers: module .to(bf16) must not downcast the f32 trig tables

@@ -30,6 +30,7 @@ HIP_SOURCES = [
     "sampling.hip",
     "conv3x3.hip",
     "moe.hip",
+    "linear_w4.hip",
 ]
 
 

@@ -84,6 +84,11 @@ int moe_route_f32(const float*, float*, int*, long long, int, int,
 int moe_ffn_bf16(const void*, const void*, const void*, const float*,
                  const int*, int*, void*, float*, void*, long long, int, int,
                  int, int, hipStream_t);
+// linear_w4_plan: the K-slice count of a call, 0 for an unsupported shape;
+// linear_w4_bf16 returns 0 once launched, non-zero (nothing launched) else
+int linear_w4_plan(long long, int, int, int);
+int linear_w4_bf16(const void*, const void*, const void*, float*, void*,
+                   long long, int, int, int, hipStream_t);
 }
 
 namespace {
@@ -827,6 +832,61 @@ torch::Tensor moe_ffn(torch::Tensor x, torch::Tensor gate_up,
   return out;
 }
 
+// x bf16 [M,K]; qweight int32 [N,K/8] or its uint8 view [N,K/2]; scales bf16
+// [N,K/128] (format: linear_w4.hip).  splits = 0 takes the kernel's split
+// rule; a positive value forces that many K slices (tests and benchmarks
+// only — the public op never passes it).  Returns [M,N] bf16.
+torch::Tensor linear_w4(torch::Tensor x, torch::Tensor qweight,
+                        torch::Tensor scales, int64_t splits) {
+  check_bf16(x, "x");
+  check_bf16(scales, "scales");
+  TORCH_CHECK(qweight.is_cuda() && qweight.is_contiguous() &&
+                  (qweight.scalar_type() == torch::kInt32 ||
+                   qweight.scalar_type() == torch::kUInt8),
+              "linear_w4: qweight must be int32 or uint8, contiguous, on GPU");
+  TORCH_CHECK(x.dim() == 2 && qweight.dim() == 2 && scales.dim() == 2,
+              "linear_w4: x must be [M,K], qweight [N,K/8], scales [N,K/128]");
+  const int64_t per = qweight.scalar_type() == torch::kInt32 ? 8 : 2;
+  const int64_t M = x.size(0), K = x.size(1), N = qweight.size(0);
+  TORCH_CHECK(M >= 1, "linear_w4: x has no rows");
+  TORCH_CHECK(K >= 128 && K % 128 == 0, "linear_w4: K=", K,
+              " (must be a multiple of 128)");
+  TORCH_CHECK(N >= 64 && N % 64 == 0, "linear_w4: N=", N,
+              " (must be a multiple of 64)");
+  TORCH_CHECK(qweight.size(1) * per == K && scales.size(0) == N &&
+                  scales.size(1) == K / 128,
+              "linear_w4: qweight ", qweight.sizes(), " / scales ",
+              scales.sizes(), " do not match N=", N, " K=", K);
+  TORCH_CHECK(qweight.device() == x.device() && scales.device() == x.device(),
+              "linear_w4: all tensors must be on x's device");
+  TORCH_CHECK(M < (1ll << 31) && N < (1ll << 31) && K < (1ll << 31) &&
+                  splits >= 0 && splits < (1ll << 31),
+              "linear_w4: size out of range");
+  // the kernel reads 16 B fragments
+  if ((uintptr_t)x.data_ptr() % 16) x = x.clone();
+  if ((uintptr_t)qweight.data_ptr() % 16) qweight = qweight.clone();
+  const int S = linear_w4_plan(M, (int)N, (int)K, (int)splits);
+  TORCH_CHECK(S >= 1, "linear_w4: shape not supported by the kernel (M=", M,
+              " N=", N, " K=", K, " splits=", splits, ")");
+  auto out = torch::empty({M, N}, x.options());
+  torch::Tensor ws;
+  if (S > 1) ws = torch::empty({S, M, N}, x.options().dtype(torch::kFloat32));
+  int rc = linear_w4_bf16(x.data_ptr(), qweight.data_ptr(), scales.data_ptr(),
+                          S > 1 ? ws.data_ptr<float>() : nullptr,
+                          out.data_ptr(), M, (int)N, (int)K, (int)splits,
+                          cur_stream());
+  TORCH_CHECK(rc == 0, "linear_w4: shape not supported by the kernel (M=", M,
+              " N=", N, " K=", K, " splits=", splits, ")");
+  return out;
+}
+
+int64_t linear_w4_splits(int64_t M, int64_t N, int64_t K, int64_t splits) {
+  TORCH_CHECK(M < (1ll << 31) && N < (1ll << 31) && K < (1ll << 31) &&
+                  splits >= 0 && splits < (1ll << 31),
+              "linear_w4: size out of range");
+  return linear_w4_plan(M, (int)N, (int)K, (int)splits);
+}
+
 torch::Tensor sample_gumbel(torch::Tensor logits, double temperature,
                             int64_t seed) {
   TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == torch::kFloat32,
@@ -1052,6 +1112,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "MoE top-k routing: (weights fp32 [N,k], idx int32 [N,k])");
   m.def("moe_ffn", &moe_ffn,
         "fused MoE FFN: on-device schedule, grouped MFMA GEMMs, combine");
+  m.def("linear_w4", &linear_w4,
+        "int4 weight-only linear: in-register dequant, MFMA, split-K",
+        pybind11::arg("x"), pybind11::arg("qweight"), pybind11::arg("scales"),
+        pybind11::arg("splits") = 0);
+  m.def("linear_w4_splits", &linear_w4_splits,
+        "K slices linear_w4 uses for (M, N, K); 0 = unsupported shape",
+        pybind11::arg("M"), pybind11::arg("N"), pybind11::arg("K"),
+        pybind11::arg("splits") = 0);
   m.def("scale_in_dev", &scale_in_dev, "x * 1/sqrt(sigma^2+1), device sigma");
   m.def("cfg_euler_dev", &cfg_euler_dev, "graph-capturable CFG+Euler step");
   m.def("step_advance", &step_advance, "increment device step counter");

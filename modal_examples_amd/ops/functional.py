@@ -641,3 +641,97 @@ def moe_ffn(x, gate_up, down, weights, idx):
         return ref.moe_ffn_ref(x, gate_up, down, weights, idx)
     return ext.moe_ffn(x, gate_up, down, weights.float().contiguous(),
                        idx.contiguous())
+
+
+# ---- int4 weight-only linear.  Supported shapes (csrc/linear_w4.hip): K a
+# multiple of 128 (the quantization group), N a multiple of 64, any number of
+# rows >= 1, contiguous weights.  The checks below run on every device,
+# before the dispatch, so the reference path refuses exactly what the kernel
+# refuses.
+
+def _check_w4_weight(weight):
+    if weight.dim() != 2:
+        raise ValueError(f"weight must be [N, K], got {tuple(weight.shape)}")
+    if weight.dtype not in (torch.bfloat16, torch.float32):
+        raise TypeError(f"weight must be bf16 or fp32, got {weight.dtype}")
+    N, K = weight.shape
+    if K < 128 or K % 128 != 0:
+        raise ValueError(f"weight has K={K} (must be a multiple of 128)")
+    if N < 64 or N % 64 != 0:
+        raise ValueError(f"weight has N={N} (must be a multiple of 64)")
+    if not weight.is_contiguous():
+        raise ValueError("weight must be contiguous")
+
+
+def _check_w4(qweight, scales):
+    """Returns (N, K) of a packed weight."""
+    if qweight.dtype not in (torch.int32, torch.uint8):
+        raise TypeError(f"qweight must be int32 or uint8, got "
+                        f"{qweight.dtype}")
+    if scales.dtype is not torch.bfloat16:
+        raise TypeError(f"scales must be bf16, got {scales.dtype}")
+    if qweight.dim() != 2 or scales.dim() != 2:
+        raise ValueError(f"qweight must be [N, K/8] and scales [N, K/128], "
+                         f"got {tuple(qweight.shape)}, {tuple(scales.shape)}")
+    N = qweight.shape[0]
+    K = qweight.shape[1] * (8 if qweight.dtype is torch.int32 else 2)
+    if K < 128 or K % 128 != 0:
+        raise ValueError(f"qweight has K={K} (must be a multiple of 128)")
+    if N < 64 or N % 64 != 0:
+        raise ValueError(f"qweight has N={N} (must be a multiple of 64)")
+    if tuple(scales.shape) != (N, K // 128):
+        raise ValueError(f"scales must be [N={N}, K/128={K // 128}], got "
+                         f"{tuple(scales.shape)}")
+    if scales.device != qweight.device:
+        raise ValueError(f"scales is on {scales.device}, qweight on "
+                         f"{qweight.device}")
+    for name, t in (("qweight", qweight), ("scales", scales)):
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    return N, K
+
+
+def quantize_w4(weight):
+    """weight [N, K] (bf16 or fp32) -> (qweight int32 [N, K/8], scales bf16
+    [N, K/128]): symmetric 4-bit quantization in groups of 128 along K.
+
+    scale = bf16(absmax(group) / 7), 1 for an all-zero group;
+    q = clamp(round_half_even(w / scale), -8, 7); the dequantized weight is
+    float(scale) * q exactly.  The packing (eight weights to a word) is the
+    kernel's and is described at the top of csrc/linear_w4.hip;
+    `dequantize_w4` inverts it."""
+    _check_w4_weight(weight)
+    return ref.quantize_w4_ref(weight)
+
+
+def dequantize_w4(qweight, scales):
+    """The dequantized weight w_hat, fp32 [N, K], exact."""
+    _check_w4(qweight, scales)
+    return ref.dequantize_w4_ref(qweight, scales)
+
+
+def linear_w4(x, qweight, scales):
+    """x [..., K] . w_hat^T with int4 weights (quantize_w4), K2.
+
+    On the GPU in bf16 without grad this is the csrc/linear_w4.hip kernel:
+    nibbles become MFMA operands in registers, the group scale multiplies
+    each group's fp32 sum, so no dequantized weight is ever rounded; K is
+    split deterministically, the result of a row is bitwise reproducible and
+    independent of the other rows, and the call captures into a graph.
+    Anywhere else it is `linear(x, dequantize_w4(...).to(x.dtype))` on the
+    same device, which is differentiable in x.  Returns [..., N] in x's
+    dtype."""
+    N, K = _check_w4(qweight, scales)
+    if not x.is_floating_point():
+        raise TypeError(f"x must be floating point, got {x.dtype}")
+    if x.dim() < 1 or x.shape[-1] != K:
+        raise ValueError(f"x must be [..., K={K}], got {tuple(x.shape)}")
+    if x.numel() == 0:
+        raise ValueError(f"x has no rows: {tuple(x.shape)}")
+    if x.device != qweight.device:
+        raise ValueError(f"x is on {x.device}, qweight on {qweight.device}")
+    ext = _ext_for(x)
+    if ext is None:
+        return ref.linear_w4_ref(x, qweight, scales)
+    y = ext.linear_w4(x.reshape(-1, K).contiguous(), qweight, scales)
+    return y.view(*x.shape[:-1], N)

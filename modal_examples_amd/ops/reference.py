@@ -439,3 +439,96 @@ def moe_ffn_bound_ref(x, gate_up, down, weights, idx, bf16_points=False):
     if bf16_points:
         out = out.to(torch.bfloat16).double()
     return out, tol
+
+
+# ---- int4 weight-only linear.  Format (csrc/linear_w4.hip): weights are
+# quantized symmetrically in groups of 128 along K; qweight int32 [N, K/8]
+# holds k = 8w..8w+7 in word w as unsigned nibbles u = q + 8, k offset j at
+# nibble position j/2 (j even) or 4 + j/2 (j odd); scales bf16 [N, K/128].
+
+W4_GROUP = 128
+
+
+def _w4_shifts(device, dtype):
+    """Bit offset of k offset j inside a packed word, [8]: nibble j/2 for
+    even j, 4 + j/2 for odd j.  Built by device ops only (no host tensor),
+    so unpacking can run inside a graph capture."""
+    j = torch.arange(8, device=device, dtype=dtype)
+    return ((j >> 1) + ((j & 1) << 2)) << 2
+
+
+def w4_pack(q):
+    """q integer [N, K] with values in [-8, 7] -> int32 [N, K/8]."""
+    N, K = q.shape
+    u = (q.to(torch.int64) + 8).view(N, K // 8, 8)
+    shifts = _w4_shifts(q.device, torch.int64)
+    word = (u << shifts).sum(-1)
+    word = torch.where(word >= 1 << 31, word - (1 << 32), word)
+    return word.to(torch.int32)
+
+
+def w4_unpack(qweight):
+    """int32 [N, K/8] (or its uint8 view [N, K/2]) -> q int32 [N, K] with
+    values in [-8, 7]; the exact inverse of w4_pack."""
+    if qweight.dtype is torch.uint8:
+        qweight = qweight.view(torch.int32)
+    shifts = _w4_shifts(qweight.device, torch.int32)
+    u = (qweight.unsqueeze(-1) >> shifts) & 0xF
+    return (u - 8).view(qweight.shape[0], -1)
+
+
+def quantize_w4_ref(weight):
+    """weight [N, K] -> (qweight int32 [N, K/8], scales bf16 [N, K/128]).
+    scale = bf16(absmax(group) / 7), 1 where that is zero (an all-zero
+    group); q = clamp(round_half_even(w / scale), -8, 7) with the quotient
+    taken in fp64, so a tie is a tie of the real quotient."""
+    N, K = weight.shape
+    g = weight.detach().double().view(N, K // W4_GROUP, W4_GROUP)
+    scales = (g.abs().amax(-1).float() / 7.0).to(torch.bfloat16)
+    scales = torch.where(scales == 0, torch.ones_like(scales), scales)
+    q = torch.round(g / scales.double().unsqueeze(-1)).clamp_(-8, 7)
+    return w4_pack(q.view(N, K)), scales
+
+
+def dequantize_w4_ref(qweight, scales):
+    """w_hat fp32 [N, K] = float(scale[n, k // 128]) * q[n, k], exact: a
+    bf16 times a 4-bit integer fits in fp32."""
+    q = w4_unpack(qweight)
+    N, K = q.shape
+    w = q.view(N, K // W4_GROUP, W4_GROUP).float() \
+        * scales.float().unsqueeze(-1)
+    return w.view(N, K)
+
+
+def linear_w4_ref(x, qweight, scales):
+    """x [..., K] . w_hat^T with w_hat cast to x's dtype (exact for fp32 and
+    wider; one rounding per weight for bf16).  Differentiable in x."""
+    w = dequantize_w4_ref(qweight, scales).to(x.dtype)
+    return torch.nn.functional.linear(x, w)
+
+
+def linear_w4_bound_ref(x, qweight, scales, bf16_points=False):
+    """(want, tol) in fp64 for an implementation of x [M, K] . w_hat^T that
+    keeps w_hat exact, accumulates in fp32 and rounds the output to bf16.
+
+      want   x . w_hat^T
+      A      |x| . |w_hat|^T
+      tol    2^-7 * |want| + 2^-10 * A
+
+    Rounding the output to bf16 moves it by at most 2^-8 * |want|; the first
+    term is twice that.  Worst-case fp32 accumulation is about K * 2^-24 * A,
+    at most 2^-10 * A up to K = 16384; the second term is also half of what
+    rounding every dequantized weight to bf16 in the worst direction could
+    do (2^-9 * A).
+
+    bf16_points=True returns the same fp64 product with the output rounded
+    to bf16 in place of `want`: the yardstick that shows how much of tol a
+    correct implementation uses."""
+    xw = x.detach().double().cpu()
+    w = dequantize_w4_ref(qweight.cpu(), scales.cpu()).double()
+    want = xw @ w.T
+    A = xw.abs() @ w.abs().T
+    tol = 2.0 ** -7 * want.abs() + 2.0 ** -10 * A
+    if bf16_points:
+        want = want.to(torch.bfloat16).double()
+    return want, tol

@@ -25,6 +25,9 @@ def main():
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--small", action="store_true")
     ap.add_argument("--kv-dtype", choices=("bf16", "fp8"), default="bf16")
+    ap.add_argument("--weight-dtype", choices=("bf16", "int4"),
+                    default="bf16",
+                    help="int4: 4-bit block projections (ops.linear_w4)")
     ap.add_argument("--spec", type=int, default=0,
                     help="ngram speculative tokens (eager decode path)")
     ap.add_argument("--prefix-cache", action="store_true")
@@ -53,7 +56,8 @@ def main():
                       max_batch=args.requests, kv_dtype=args.kv_dtype,
                       spec_tokens=args.spec,
                       prefix_cache=args.prefix_cache,
-                      chunked_prefill=args.chunked)
+                      chunked_prefill=args.chunked,
+                      weight_dtype=args.weight_dtype)
     eng.warmup()  # decode-graph capture is cold-start work
     if device == "cuda":
         torch.cuda.synchronize()
@@ -90,6 +94,9 @@ def main():
         "output_tok_per_s": round(out_toks / dt, 1),
         "kv_blocks": eng.num_blocks,
         "kv_dtype": args.kv_dtype,
+        "weight_dtype": args.weight_dtype,
+        "weight_bytes": sum(t.numel() * t.element_size()
+                            for t in eng.model.state_dict().values()),
         "hipgraph": eng.use_graph,
         "spec": {"proposed": eng.spec_proposed, "accepted": eng.spec_accepted}
         if args.spec else None,

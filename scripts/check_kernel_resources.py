@@ -48,6 +48,12 @@ OCCUPANCY_FLOORS = {
     "moe_route_kernel": 8,
     "moe_align_kernel": 8,
     "moe_combine_kernel": 8,
+    # w4_gemm_kernel: two register sets of a 128-deep chunk (x fragments,
+    # packed words, scales) beside 32 accumulators and the group's 48 partial
+    # sums; built for two waves per SIMD (242 VGPRs), the second wave hides
+    # a chunk's load latency
+    "w4_gemm_kernel": 2,
+    "w4_reduce_kernel": 8,
 }
 
 
