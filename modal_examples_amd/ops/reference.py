@@ -148,6 +148,53 @@ def attention_bwd_ref(q, k, v, o, lse, dout, causal: bool = False,
     return rnd(dq), rnd(dk), rnd(dv)
 
 
+def attention_bwd_bound_ref(q, k, v, o, lse, dout, causal: bool = False,
+                            scale: Optional[float] = None):
+    """The magnitudes a per-element error bound of a bf16 attention backward
+    is made of, in fp64 (inputs as for attention_bwd_ref, any dtype):
+
+      P       [B,Hq,Sq,Sk]  exp(s*scale - lse), 0 where masked
+      E_q     [B,Hq,Sq]     sum_d |dO|*|O|: what delta = sum_d dO*O is made of
+      dS_abs  [B,Hq,Sq,Sk]  |dS| + P*E_q, dS = P o (dP - delta): the size of
+                            dS plus what one relative rounding of o moves it
+                            by through delta
+      A_dv    [B,Hkv,Sk,D]  P^T.|dO| summed over the GQA group
+      A_dk    [B,Hkv,Sk,D]  |scale| * dS_abs^T.|Q| summed over the group
+      A_dq    [B,Hq,Sq,D]   |scale| * dS_abs.|K|
+      M       float         max over visible pairs of |s*scale| + |lse|: the
+                            size of the exponential's argument before the
+                            subtraction
+
+    A_* are the absolute-value propagations of P and dS through the output
+    products: an implementation that rounds P (dV) or dS (dQ, dK) and the
+    output to bf16 errs by at most 2^-8 * (A + |truth|) from those two
+    roundings if every one of them errs fully and in the worst direction."""
+    B, Hq, Sq, D = q.shape
+    Hkv, Sk = k.shape[1], k.shape[2]
+    G = Hq // Hkv
+    scale = scale if scale is not None else 1.0 / math.sqrt(D)
+    q, k, v, o, dout = (t.double() for t in (q, k, v, o, dout))
+    lse = lse.double().reshape(B, Hkv, G, Sq, 1)
+    qg = q.reshape(B, Hkv, G, Sq, D)
+    og = o.reshape(B, Hkv, G, Sq, D)
+    dog = dout.reshape(B, Hkv, G, Sq, D)
+    kg, vg = k.unsqueeze(2), v.unsqueeze(2)
+    s = _masked_scores(q, k, causal, scale)  # [B,Hkv,G,Sq,Sk]
+    seen = s > float("-inf")
+    p = torch.exp(s - lse)  # masked -> 0
+    arg = torch.where(seen, s.abs() + lse.abs(), torch.zeros_like(s))
+    e_q = (dog.abs() * og.abs()).sum(-1, keepdim=True)
+    delta = (dog * og).sum(-1, keepdim=True)
+    ds = p * (torch.matmul(dog, vg.transpose(-1, -2)) - delta)
+    ds_abs = ds.abs() + p * e_q
+    a_dv = torch.matmul(p.transpose(-1, -2), dog.abs()).sum(2)
+    a_dk = torch.matmul(ds_abs.transpose(-1, -2), qg.abs()).sum(2) * abs(scale)
+    a_dq = (torch.matmul(ds_abs, kg.abs()) * abs(scale)).reshape(B, Hq, Sq, D)
+    return dict(P=p.reshape(B, Hq, Sq, Sk), E_q=e_q.reshape(B, Hq, Sq),
+                dS_abs=ds_abs.reshape(B, Hq, Sq, Sk), A_dv=a_dv, A_dk=a_dk,
+                A_dq=a_dq, M=float(arg.max()))
+
+
 def paged_decode_ref(q, k_cache, v_cache, block_table, seq_lens, block_size,
                      scale: Optional[float] = None):
     """q [B,Hq,D]; paged cache [nblocks,Hkv,block_size,D] (+table) or
