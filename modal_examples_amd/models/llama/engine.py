@@ -27,8 +27,9 @@ from typing import Dict, List, Optional
 import torch
 
 from ...ops import functional as OF
-from .model import (WEIGHT_DTYPES, LlamaConfig, LlamaModel, MoEFFN,
-                    quantize_llama_, quantize_llama_state)
+from .model import (EXPERT_DTYPES, WEIGHT_DTYPES, LlamaConfig, LlamaModel,
+                    MoEFFN, quantize_llama_, quantize_llama_expert_state,
+                    quantize_llama_experts_, quantize_llama_state)
 
 BLOCK = 16
 
@@ -81,7 +82,8 @@ class LlamaEngine:
                  gpu_mem_util: float = 0.6,
                  prefill_attn: str = "decode",
                  moe_impl: Optional[str] = None,
-                 weight_dtype: str = "bf16"):
+                 weight_dtype: str = "bf16",
+                 expert_dtype: Optional[str] = None):
         """tp: optional parallel.tp.TPGroup — head-sharded tensor parallelism
         (vllm_inference.py:180 --tensor-parallel-size role).  Every rank runs
         the same engine loop on identical requests; the KV cache holds only
@@ -136,8 +138,21 @@ class LlamaEngine:
         the freed memory; with init_weights=False the model is built with
         empty packed buffers for load_state_dict(assign=True).  Under tp the
         shards are quantized, and a shard whose input width is no multiple
-        of 128 raises.  MoE configs raise ValueError (int4 experts are not
-        implemented).
+        of 128 raises.  MoE configs raise ValueError: their experts have a
+        knob of their own, expert_dtype.
+
+        expert_dtype: "bf16" or "int4"; None keeps cfg.expert_dtype.  "int4"
+        holds the experts of every MoE block as 4-bit weights with one bf16
+        scale per 128 inputs (ops.quantize_w4_experts; model.MoEFFN): 0.52
+        bytes per expert weight instead of 2, with the router, qkv and o_proj
+        left in `dtype`.  It needs moe_impl="fused" and an MoE config (both
+        ValueError otherwise).  Batches up to MoEFFN.N_KERNEL tokens run on
+        the int4 grouped GEMMs of csrc/moe.hip (ops.moe_ffn_w4), inside the
+        decode graph like the fused bf16 lane; larger ones (prefill)
+        dequantize each active expert into a scratch and use the ordinary
+        GEMMs.  With init_weights=True the experts are quantized in place
+        before the KV pool is sized; with init_weights=False the model is
+        built with empty packed buffers.
 
         gpu_mem_util: fraction of free HBM the KV pool claims when
         kv_blocks is unset (--gpu-memory-utilization / --mem-fraction-static
@@ -156,6 +171,21 @@ class LlamaEngine:
                              "experts; use weight_dtype='bf16' for an MoE "
                              "config")
         self.weight_dtype = weight_dtype
+        if expert_dtype is None:
+            expert_dtype = self.cfg.expert_dtype
+        if expert_dtype not in EXPERT_DTYPES:
+            raise ValueError(f"expert_dtype must be one of {EXPERT_DTYPES}, "
+                             f"got {expert_dtype!r}")
+        if expert_dtype == "int4":
+            if self.cfg.n_experts <= 0:
+                raise ValueError("expert_dtype='int4' needs an MoE config "
+                                 "(n_experts > 0); weight_dtype='int4' is "
+                                 "the dense model's knob")
+            if self.cfg.moe_impl != "fused":
+                raise ValueError("expert_dtype='int4' needs moe_impl='fused',"
+                                 f" got moe_impl={self.cfg.moe_impl!r}")
+        self.cfg = dataclasses.replace(self.cfg, expert_dtype=expert_dtype)
+        self.expert_dtype = expert_dtype
         self.tp = tp
         self.spec_tokens = spec_tokens
         self.spec_proposed = 0   # drafts offered
@@ -194,9 +224,14 @@ class LlamaEngine:
         torch.manual_seed(seed)
         if init_weights:
             with torch.device(self.device):
-                self.model = LlamaModel(self.cfg, tp=tp).to(self.device, dtype)
-            if weight_dtype == "int4":
-                quantize_llama_(self.model)
+                self.model = LlamaModel(
+                    dataclasses.replace(self.cfg, expert_dtype="bf16"),
+                    tp=tp).to(self.device, dtype)
+            if weight_dtype == "int4" or expert_dtype == "int4":
+                if weight_dtype == "int4":
+                    quantize_llama_(self.model)
+                else:
+                    quantize_llama_experts_(self.model)
                 if self.device.type == "cuda":
                     # hand the bf16 projections back before the pool is sized
                     torch.cuda.empty_cache()
@@ -270,7 +305,9 @@ class LlamaEngine:
     def save_safetensors(self, path: str) -> int:
         """Bake the weights for `from_safetensors` (the snapshot-build step;
         reference role: sglang_snapshot.py:176-218 warm/sleep/wake).  An
-        int4 engine writes its packed `qweight` / `scales` tensors."""
+        int4 engine writes its packed `qweight` / `scales` tensors, an
+        int4-expert engine its `gate_up_q` / `gate_up_s` / `down_q` /
+        `down_s` buffers."""
         from ...gpu import fastload
 
         return fastload.save_file(dict(self.model.state_dict()), path)
@@ -289,7 +326,10 @@ class LlamaEngine:
         holds; asking for "bf16" raises, and so does tp.world > 1, whose
         shards would cut through packed words).  A bf16 file with
         weight_dtype="int4" is sharded first, if tp is set, and then
-        quantized on the device."""
+        quantized on the device.  The same holds for expert_dtype: a file
+        with `.gate_up_q` keys defaults it to "int4" and refuses "bf16", and
+        a bf16 file with expert_dtype="int4" is quantized on the device after
+        loading."""
         import threading
 
         from ...gpu import fastload
@@ -300,6 +340,13 @@ class LlamaEngine:
         if packed and kw["weight_dtype"] != "int4":
             raise ValueError(f"{path} holds int4 weights; it cannot boot a "
                              f"weight_dtype={kw['weight_dtype']!r} engine")
+        packed_experts = any(k.endswith(".gate_up_q") for k in header)
+        if packed_experts:
+            kw.setdefault("expert_dtype", "int4")
+            if kw["expert_dtype"] != "int4":
+                raise ValueError(f"{path} holds int4 experts; it cannot boot "
+                                 f"an expert_dtype={kw['expert_dtype']!r} "
+                                 f"engine")
         tp = kw.get("tp")
         if packed and tp is not None and tp.world > 1:
             raise ValueError("loading an int4 checkpoint under tensor "
@@ -330,6 +377,8 @@ class LlamaEngine:
             sd = {k: v.contiguous() for k, v in sd.items()}
         if eng.weight_dtype == "int4" and not packed:
             sd = quantize_llama_state(sd)
+        if eng.expert_dtype == "int4" and not packed_experts:
+            sd = quantize_llama_expert_state(sd)
         eng.model.load_state_dict(sd, assign=True)
         return eng
 

@@ -12,6 +12,7 @@ MI355X mapping:
 """
 from __future__ import annotations
 
+import dataclasses
 from dataclasses import dataclass
 
 import torch
@@ -36,6 +37,7 @@ class LlamaConfig:
     n_experts: int = 0   # >0: MoE FFN (Mixtral/DeepSeek-class)
     experts_per_tok: int = 2
     moe_impl: str = "loop"  # MoEFFN forward: "loop" or "fused" (ops.moe_ffn)
+    expert_dtype: str = "bf16"  # MoE expert weights: "bf16" or "int4"
 
     @staticmethod
     def llama3_8b() -> "LlamaConfig":
@@ -55,6 +57,7 @@ class LlamaConfig:
 
 
 WEIGHT_DTYPES = ("bf16", "int4")
+EXPERT_DTYPES = ("bf16", "int4")
 
 
 class QuantLinear(nn.Module):
@@ -162,6 +165,37 @@ def quantize_llama_state(state: dict) -> dict:
     return out
 
 
+def quantize_llama_experts_(model: "LlamaModel") -> "LlamaModel":
+    """Quantize the experts of every MoE block in place
+    (MoEFFN.quantize_experts_), one matrix at a time so the bf16 copy of each
+    is released as it goes.  Router, attention projections, embedding, norms
+    and lm_head stay as they are."""
+    if model.cfg.n_experts <= 0:
+        raise ValueError("expert_dtype='int4' needs an MoE config "
+                         "(n_experts > 0)")
+    for blk in model.blocks:
+        blk.moe.quantize_experts_()
+    model.cfg = dataclasses.replace(model.cfg, expert_dtype="int4")
+    return model
+
+
+def quantize_llama_expert_state(state: dict) -> dict:
+    """A bf16 state dict of an MoE LlamaModel with every block's
+    `moe.gate_up` / `moe.down` replaced by its `_q` / `_s` pair."""
+    out = {}
+    for k, v in state.items():
+        parts = k.split(".")
+        if (len(parts) == 4 and parts[0] == "blocks" and parts[2] == "moe"
+                and parts[3] in ("gate_up", "down")):
+            if v.dtype not in (torch.bfloat16, torch.float32):
+                v = v.float()
+            out[k + "_q"], out[k + "_s"] = OF.quantize_w4_experts(
+                v.contiguous())
+        else:
+            out[k] = v
+    return out
+
+
 class LlamaBlock(nn.Module):
     def __init__(self, cfg: LlamaConfig, tp_world: int = 1,
                  weight_dtype: str = "bf16"):
@@ -198,7 +232,8 @@ class LlamaBlock(nn.Module):
         if cfg.n_experts > 0:
             assert tp_world == 1, "MoE + TP not supported (EP is a non-goal)"
             self.moe = MoEFFN(d, cfg.ffn_dim, cfg.n_experts,
-                              cfg.experts_per_tok, impl=cfg.moe_impl)
+                              cfg.experts_per_tok, impl=cfg.moe_impl,
+                              expert_dtype=cfg.expert_dtype)
             self.gate_up = self.down = None
         else:
             self.moe = None
@@ -368,23 +403,120 @@ class MoEFFN(nn.Module):
     device (csrc/moe.hip), sync-free and capturable; the routing weights
     stay fp32 and each token's expert outputs are summed in fp32.  Shared
     experts, expert parallelism and fp8 expert weights are not supported by
-    either."""
+    either.
+
+    expert_dtype="int4" (impl="fused" only) holds the experts as 4-bit
+    weights with one bf16 scale per 128 inputs (ops.quantize_w4_experts) in
+    four buffers, gate_up_q / gate_up_s / down_q / down_s, instead of the two
+    Parameters: 0.52 bytes per weight.  The router stays as it is.  Two
+    lanes.  Up to N_KERNEL tokens (decode, speculative verification, small
+    chunks) the forward is ops.moe_route -> ops.moe_ffn_w4: the int4 grouped
+    GEMMs of csrc/moe.hip, which apply each group's scale to its fp32 partial
+    sum and never round a dequantized weight.  Above that (prefill) it is the
+    host loop over the active experts, each expert's two matrices
+    dequantized into a reusable scratch of the activation dtype just before
+    its GEMMs; in bf16 that rounds every scale * q to bf16, like
+    QuantLinear's prefill lane, so the two lanes differ by that rounding (in
+    fp32 they are the same products).  The prefill lane reads the routing
+    back to the host; decode stays under N_KERNEL and captures."""
 
     IMPLS = ("loop", "fused")
 
+    # tokens up to which the int4 kernel lane is taken.  Measured at the
+    # benchmark's expert shape (profiles/moe_ffn_w4.txt, "crossover" lines):
+    # the dequantize-and-loop lane pays about 4.6 ms for dequantizing eight
+    # experts whatever N, and the kernel lane is still ahead at 4096 tokens
+    # (3147 / 5419 us; 1596 / 5092 at 2048).  4096 is the largest measured
+    # count, and it is on the kernel's side; the crossover lies above it.
+    N_KERNEL = 4096
+
     def __init__(self, dim: int, ffn_dim: int, n_experts: int, top_k: int,
-                 impl: str = "loop"):
+                 impl: str = "loop", expert_dtype: str = "bf16"):
         super().__init__()
         if impl not in self.IMPLS:
             raise ValueError(f"moe impl must be one of {self.IMPLS}, got "
                              f"{impl!r}")
+        if expert_dtype not in EXPERT_DTYPES:
+            raise ValueError(f"expert_dtype must be one of {EXPERT_DTYPES}, "
+                             f"got {expert_dtype!r}")
         self.impl = impl
+        self.expert_dtype = "bf16"
+        self.dim, self.ffn_dim = dim, ffn_dim
+        self.n_experts, self.top_k = n_experts, top_k
         self.router = nn.Linear(dim, n_experts, bias=False)
+        if expert_dtype == "int4":
+            # empty packed buffers, for loading a quantized state
+            self._check_int4()
+            self.gate_up = self.down = None
+            self._set_packed(
+                torch.zeros(n_experts, 2 * ffn_dim, dim // 8, dtype=torch.int32),
+                torch.ones(n_experts, 2 * ffn_dim, dim // 128,
+                           dtype=torch.bfloat16),
+                torch.zeros(n_experts, dim, ffn_dim // 8, dtype=torch.int32),
+                torch.ones(n_experts, dim, ffn_dim // 128,
+                           dtype=torch.bfloat16))
+            return
         self.gate_up = nn.Parameter(
             torch.empty(n_experts, 2 * ffn_dim, dim).normal_(std=0.02))
         self.down = nn.Parameter(
             torch.empty(n_experts, dim, ffn_dim).normal_(std=0.02))
-        self.n_experts, self.top_k = n_experts, top_k
+
+    def _check_int4(self):
+        if self.impl != "fused":
+            raise ValueError("expert_dtype='int4' needs moe_impl='fused', got "
+                             f"moe_impl={self.impl!r}")
+        if self.dim % 128 or self.ffn_dim % 128:
+            raise ValueError(f"expert_dtype='int4' needs dim={self.dim} and "
+                             f"ffn_dim={self.ffn_dim} to be multiples of the "
+                             f"int4 group size 128")
+
+    def _set_packed(self, gate_up_q, gate_up_s, down_q, down_s):
+        for name, t in (("gate_up_q", gate_up_q), ("gate_up_s", gate_up_s),
+                        ("down_q", down_q), ("down_s", down_s)):
+            self.register_buffer(name, t)
+        self.expert_dtype = "int4"
+        self._scratch = {}
+
+    def quantize_experts_(self) -> "MoEFFN":
+        """Convert an initialised bf16-expert module in place, one matrix at
+        a time, and free the two Parameters."""
+        if self.expert_dtype == "int4":
+            return self
+        self._check_int4()
+        packed = []
+        for name in ("gate_up", "down"):
+            w = getattr(self, name).detach()
+            if w.dtype not in (torch.bfloat16, torch.float32):
+                w = w.float()
+            setattr(self, name, None)  # drops the Parameter
+            packed.extend(OF.quantize_w4_experts(w.contiguous()))
+            del w
+        self._set_packed(*packed)
+        return self
+
+    def _apply(self, fn, recurse=True):
+        # module.to(dtype) casts every floating buffer; the scales are bf16
+        # by format (a round trip through a wider type loses nothing)
+        super()._apply(fn, recurse)
+        if self.expert_dtype == "int4":
+            for name in ("gate_up_s", "down_s"):
+                t = getattr(self, name)
+                if t.dtype is not torch.bfloat16:
+                    setattr(self, name, t.to(torch.bfloat16))
+            self._scratch = {}
+        return self
+
+    def _dequantized(self, name, e, dtype):
+        """Expert e's matrix `name` in `dtype`, in a scratch reused across
+        experts and calls (one per matrix)."""
+        q, s = getattr(self, name + "_q")[e], getattr(self, name + "_s")[e]
+        buf = self._scratch.get(name)
+        if buf is None or buf.dtype is not dtype or buf.device != q.device:
+            buf = torch.empty(q.shape[0], q.shape[1] * 8, dtype=dtype,
+                              device=q.device)
+            self._scratch[name] = buf
+        buf.copy_(OF.dequantize_w4(q, s))
+        return buf
 
     def forward(self, x):
         from ...ops import functional as OF
@@ -392,7 +524,13 @@ class MoEFFN(nn.Module):
         B, S, d = x.shape
         flat = x.reshape(-1, d)
         scores = self.router(flat).float()                  # [N, E]
-        if self.impl == "fused":
+        int4 = self.expert_dtype == "int4"
+        if int4 and flat.shape[0] <= self.N_KERNEL:
+            w, idx = OF.moe_route(scores, self.top_k)
+            return OF.moe_ffn_w4(flat.contiguous(), self.gate_up_q,
+                                 self.gate_up_s, self.down_q, self.down_s, w,
+                                 idx).view(B, S, d)
+        if self.impl == "fused" and not int4:
             w, idx = OF.moe_route(scores, self.top_k)
             return OF.moe_ffn(flat.contiguous(), self.gate_up, self.down, w,
                               idx).view(B, S, d)
@@ -403,6 +541,11 @@ class MoEFFN(nn.Module):
             hit = (idx == e)                                # [N, k]
             rows = hit.any(-1).nonzero(as_tuple=True)[0]
             contrib = (w * hit).sum(-1)[rows].unsqueeze(-1)  # routed weight
-            h = OF.glu_fused(flat[rows] @ self.gate_up[e].T, gelu=False)
-            out[rows] += contrib * (h @ self.down[e].T)
+            if int4:
+                gate_up = self._dequantized("gate_up", e, x.dtype)
+                down = self._dequantized("down", e, x.dtype)
+            else:
+                gate_up, down = self.gate_up[e], self.down[e]
+            h = OF.glu_fused(flat[rows] @ gate_up.T, gelu=False)
+            out[rows] += contrib * (h @ down.T)
         return out.view(B, S, d)

@@ -44,82 +44,16 @@
 // a function of (N, K) only (linear_w4_plan), there are no float atomics and
 // a row's sums never see another row: the result of a row is bitwise
 // reproducible and independent of M and of the M-tile it falls into.
-#include "attention_mfma32.h"
+#include "w4_mma.h"  // W4_G, W4_BIAS, w4_load, w4_unpack, w4_mma, w4_groups
 
 #define W4_BM 32
-#define W4_G 128           // quantization group = K-chunk
-#define W4_BIAS 136.f      // 128 from the exponent trick + 8 from u = q + 8
 // waves the split rule aims for (profiles/linear_w4.txt)
 #define W4_TARGET_WAVES 512
-
-struct W4Frags {
-  bf16x8 a[8];
-  i32x4 b0[2], b1[2];
-  unsigned short s0, s1;
-};
-
-DEV_INLINE void w4_load(W4Frags& f, const short* pa, const int* p0,
-                        const int* p1, const unsigned short* ps0,
-                        const unsigned short* ps1, int ch, short keep) {
-  const int* w0 = p0 + ch * (W4_G / 8);
-  const int* w1 = p1 + ch * (W4_G / 8);
-  f.b0[0] = *(const i32x4*)w0;
-  f.b0[1] = *(const i32x4*)(w0 + 4);
-  f.b1[0] = *(const i32x4*)w1;
-  f.b1[1] = *(const i32x4*)(w1 + 4);
-  f.s0 = ps0[ch];
-  f.s1 = ps1[ch];
-  const short* a = pa + ch * W4_G;
-  // keep is all ones, or zero on a row past M: a mask, not a select, so the
-  // load itself stays unconditional
-#pragma unroll
-  for (int s = 0; s < 8; ++s) f.a[s] = *(const bf16x8*)(a + s * 8) & keep;
-}
-
-// one packed word -> the bf16 fragment {136+q(k+0), ..., 136+q(k+7)}
-DEV_INLINE bf16x8 w4_unpack(int word) {
-  const unsigned w = (unsigned)word;
-  union {
-    unsigned d[4];
-    bf16x8 v;
-  } u;
-  u.d[0] = (w & 0x000F000Fu) | 0x43004300u;
-  u.d[1] = ((w >> 4) & 0x000F000Fu) | 0x43004300u;
-  u.d[2] = ((w >> 8) & 0x000F000Fu) | 0x43004300u;
-  u.d[3] = ((w >> 12) & 0x000F000Fu) | 0x43004300u;
-  return u.v;
-}
-
-// one group: biased products P and row sums X by MFMA, then
-// acc += scale * (P - 136 X) in fp32
-DEV_INLINE void w4_mma(const W4Frags& f, f32x16& acc0, f32x16& acc1) {
-  const short one = 0x3F80;
-  const bf16x8 ones = {one, one, one, one, one, one, one, one};
-  f32x16 p0, p1, xs;
-#pragma unroll
-  for (int r = 0; r < 16; ++r) p0[r] = p1[r] = xs[r] = 0.f;
-#pragma unroll
-  for (int s = 0; s < 8; ++s) {
-    bf16x8 b0 = w4_unpack(f.b0[s >> 2][s & 3]);
-    bf16x8 b1 = w4_unpack(f.b1[s >> 2][s & 3]);
-    p0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[s], b0, p0, 0, 0, 0);
-    p1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[s], b1, p1, 0, 0, 0);
-    xs = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f.a[s], ones, xs, 0, 0, 0);
-  }
-  const float s0 = bf2f((short)f.s0), s1 = bf2f((short)f.s1);
-#pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    acc0[r] = __builtin_fmaf(s0, __builtin_fmaf(-W4_BIAS, xs[r], p0[r]),
-                             acc0[r]);
-    acc1[r] = __builtin_fmaf(s1, __builtin_fmaf(-W4_BIAS, xs[r], p1[r]),
-                             acc1[r]);
-  }
-}
 
 // grid = mtiles * (N/64) * S, M-tile fastest so the waves that share a
 // weight tile run together.  cps = groups per slice.  S == 1: Y bf16 [M,N];
 // S > 1: WS f32 [S,M,N].  Left alone the allocator takes 296 registers (one
-// wave per SIMD); asked for two waves it fits 242 without a spill, and the
+// wave per SIMD); asked for two waves it fits 249 without a spill, and the
 // second wave is what hides a chunk's load latency.
 __global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(2, 2)))
 void w4_gemm_kernel(
@@ -140,32 +74,16 @@ void w4_gemm_kernel(
   const size_t a_row = row < M ? (size_t)row : 0;
   const int n0 = nb * 64, n1 = n0 + 32;
   const short* pa = X + a_row * K + hi5 * 64;
-  const int* p0 = QW + (size_t)(n0 + l31) * (K / 8) + hi5 * 8;
-  const int* p1 = QW + (size_t)(n1 + l31) * (K / 8) + hi5 * 8;
-  const unsigned short* ps0 = SC + (size_t)(n0 + l31) * nch;
-  const unsigned short* ps1 = SC + (size_t)(n1 + l31) * nch;
+  const int* const p[2] = {QW + (size_t)(n0 + l31) * (K / 8) + hi5 * 8,
+                           QW + (size_t)(n1 + l31) * (K / 8) + hi5 * 8};
+  const unsigned short* const ps[2] = {SC + (size_t)(n0 + l31) * nch,
+                                       SC + (size_t)(n1 + l31) * nch};
 
-  f32x16 acc0, acc1;
+  f32x16 acc[2];
 #pragma unroll
-  for (int r = 0; r < 16; ++r) acc0[r] = acc1[r] = 0.f;
-
-  // two register sets in turn, groups ascending: f0 holds group c, f1 c + 1
-  W4Frags f0, f1;
-  w4_load(f0, pa, p0, p1, ps0, ps1, ch0, keep);
-  int c = ch0;
-  for (; c + 2 < ch1; c += 2) {
-    w4_load(f1, pa, p0, p1, ps0, ps1, c + 1, keep);
-    w4_mma(f0, acc0, acc1);
-    w4_load(f0, pa, p0, p1, ps0, ps1, c + 2, keep);
-    w4_mma(f1, acc0, acc1);
-  }
-  if (c + 1 < ch1) {
-    w4_load(f1, pa, p0, p1, ps0, ps1, c + 1, keep);
-    w4_mma(f0, acc0, acc1);
-    w4_mma(f1, acc0, acc1);
-  } else {
-    w4_mma(f0, acc0, acc1);
-  }
+  for (int r = 0; r < 16; ++r) acc[0][r] = acc[1][r] = 0.f;
+  w4_groups<2>(acc, pa, p, ps, ch0, ch1, keep);
+  const f32x16 &acc0 = acc[0], &acc1 = acc[1];
 
   // C fragment: register r of this lane is row c_row(r, hi5), column l31
   if (S == 1) {

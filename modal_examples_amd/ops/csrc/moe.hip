@@ -32,10 +32,25 @@
 // 6 B * E*F*d of weights — 0.25 % of the bytes at N=64, and one rounding
 // fewer than a bf16 y.
 //
+// Int4 experts (moe_ffn_w4_bf16): the same schedule, work split and
+// epilogues over linear_w4.hip's packed format with a leading expert
+// dimension — gate_up_q int32 [E,2F,d/8] + gate_up_s bf16 [E,2F,d/128],
+// down_q int32 [E,d,F/8] + down_s bf16 [E,d,F/128] — and w4_mma.h's inner
+// loop: a chunk is one group of 128 k, the nibbles become 136+q MFMA operands
+// in registers, a third MFMA per k-step against ones gives the group's row
+// sum X_g (shared by the wave's N-tiles), and acc += s * (P_g - 136 X_g) runs
+// in fp32 once per group with each tile's own scale.  No dequantized weight
+// is ever rounded.  A wave has a quarter of the bf16 kernel's bytes to hide
+// its latency behind, so the down GEMM cuts K into MOE_W4_DOWN_SLICES
+// contiguous slices, one wave each, whose fp32 partials land in separate y
+// planes that the combine sums in ascending order (profiles/moe_ffn_w4.txt
+// has the alternatives).  The slice count depends on ffn_dim only, so the
+// contract above holds unchanged.
+//
 // Preconditions the device cannot report: idx values in [0,E), distinct per
 // token (moe_route always produces that).  A pair with an id outside [0,E)
 // is skipped by align — its y row is never written — rather than indexed.
-#include "attention_mfma32.h"
+#include "w4_mma.h"  // attention_mfma32.h + the int4 group recipe
 
 #define MOE_BM 32          // rows per M-tile = one 32x32 MFMA tile
 #define MOE_MAX_E 128
@@ -252,6 +267,84 @@ __global__ __launch_bounds__(WAVE) void moe_gemm_kernel(
   }
 }
 
+// ---------------------------------------------------------------- int4 GEMM
+// moe_gemm_kernel's work split over int4 weights: one wave per block, M-tile
+// mtile x two 32-column N-tiles, over the groups of K slice z.  UP (one
+// slice): gate columns n0.. and up columns Nout+n0.., A rows gathered
+// through the slot map, silu(gate)*up to H.  !UP: 64 adjacent columns, A rows
+// in slot order, the slice's fp32 partial of each row to its pair's row of
+// plane z of Y [S][P][Nout].  cps = groups per slice.  Built for two waves
+// per SIMD like w4_gemm_kernel: the second wave hides a group's load latency.
+
+template <bool UP>
+__global__ __launch_bounds__(WAVE) __attribute__((amdgpu_waves_per_eu(2, 2)))
+W4_NO_PK_F32 void moe_gemm_w4_kernel(
+    const short* __restrict__ A, const int* __restrict__ QW,
+    const unsigned short* __restrict__ SC, const int* __restrict__ slot_map,
+    const int* __restrict__ tile_expert, const int* __restrict__ num_tiles,
+    short* __restrict__ H, float* __restrict__ Y, int K, int Nout, int top_k,
+    int max_tiles, int cps, long long plane) {
+  constexpr int NT = 2;
+  const int mtile = blockIdx.x % max_tiles;
+  if (mtile >= *num_tiles) return;  // tiles past the device-side count
+  const int rest = blockIdx.x / max_tiles;
+  const int nblocks = Nout / (UP ? 32 : 64);
+  const int nb = rest % nblocks, z = rest / nblocks;
+  const int lane = threadIdx.x, l31 = lane & 31, hi5 = lane >> 5;
+  const int e = tile_expert[mtile];
+  const int slot = mtile * MOE_BM + l31;
+  const int pair = slot_map[slot];
+  const short keep = (UP && pair < 0) ? 0 : -1;
+  const int nch = K / W4_G;
+  const int ch0 = z * cps;
+  const int ch1 = ch0 + cps < nch ? ch0 + cps : nch;
+
+  int n[NT];  // first column of each N-tile, as rows of W[e]
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+    n[t] = UP ? t * Nout + nb * 32 : (nb * NT + t) * 32;
+  const size_t a_row = UP ? (pair < 0 ? 0 : (size_t)(pair / top_k))
+                          : (size_t)slot;
+  const size_t w_row0 = (size_t)e * (UP ? 2 * (size_t)Nout : (size_t)Nout);
+  const short* pa = A + a_row * K + hi5 * 64;
+  const int* p[NT];
+  const unsigned short* ps[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t) {
+    p[t] = QW + (w_row0 + n[t] + l31) * (K / 8) + hi5 * 8;
+    ps[t] = SC + (w_row0 + n[t] + l31) * nch;
+  }
+
+  f32x16 acc[NT];
+#pragma unroll
+  for (int t = 0; t < NT; ++t)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+  w4_groups<NT>(acc, pa, p, ps, ch0, ch1, keep);
+
+  // C fragment: register r of this lane is row c_row(r, hi5), column l31
+  if constexpr (UP) {
+    short* hrow = H + (size_t)mtile * MOE_BM * Nout + n[0] + l31;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      float g = acc[0][r], u = acc[1][r];
+      float h = g / (1.f + __expf(-g)) * u;
+      hrow[(size_t)c_row(r, hi5) * Nout] = f2bf(h);
+    }
+  } else {
+    float* yz = Y + (size_t)z * plane;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+      int pr = slot_map[mtile * MOE_BM + c_row(r, hi5)];
+      if (pr >= 0) {
+        float* yrow = yz + (size_t)pr * Nout + l31;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) yrow[n[t]] = acc[t][r];
+      }
+    }
+  }
+}
+
 // ---------------------------------------------------------------- combine
 
 __global__ __launch_bounds__(256) void moe_combine_kernel(
@@ -266,6 +359,37 @@ __global__ __launch_bounds__(256) void moe_combine_kernel(
     for (int j = 0; j < top_k; ++j) {
       float w = weights[t * top_k + j];
       f32x4 y = *(const f32x4*)&Y[((t * top_k + j) * d4 + c4) * 4];
+#pragma unroll
+      for (int q = 0; q < 4; ++q) acc[q] += w * y[q];
+    }
+    bf16x4 o;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) o[q] = f2bf(acc[q]);
+    *(bf16x4*)&out[i * 4] = o;
+  }
+}
+
+// The combine over S planes of K-slice partials, Y [S][P][d]: a pair's row is
+// summed over the slices in ascending order first, then weighted as above.
+W4_NO_PK_F32 __global__ __launch_bounds__(256) void moe_combine_planes_kernel(
+    const float* __restrict__ Y, const float* __restrict__ weights,
+    short* __restrict__ out, long long n4, int d4, int top_k, int S,
+    long long plane) {
+  long long stride = (long long)gridDim.x * 256;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4;
+       i += stride) {
+    long long t = i / d4;
+    int c4 = (int)(i % d4);
+    f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+    for (int j = 0; j < top_k; ++j) {
+      float w = weights[t * top_k + j];
+      const float* yp = &Y[((t * top_k + j) * d4 + c4) * 4];
+      f32x4 y = *(const f32x4*)yp;
+      for (int z = 1; z < S; ++z) {
+        f32x4 part = *(const f32x4*)(yp + z * plane);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) y[q] += part[q];
+      }
 #pragma unroll
       for (int q = 0; q < 4; ++q) acc[q] += w * y[q];
     }
@@ -348,5 +472,76 @@ extern "C" int moe_ffn_bf16(const void* x, const void* gate_up,
   int grid = (int)((n4 + 255) / 256 > 4096 ? 4096 : (n4 + 255) / 256);
   hipLaunchKernelGGL(moe_combine_kernel, dim3(grid), dim3(256), 0, stream,
                      (const float*)y, weights, (short*)out, n4, d / 4, top_k);
+  return 0;
+}
+
+// The K slices of the int4 lane's down GEMM for ffn_dim F (= planes of y), 0
+// for an unsupported F.  splits <= 0 asks for the rule, MOE_W4_DOWN_SLICES
+// capped at one slice per group: a function of F only.  splits > 0 (the
+// benchmark's sweep) is taken as given.  Either way the count is normalised
+// so that no slice is empty.  Measured at dim = ffn_dim = 4096, E = 8, k = 2
+// (profiles/moe_ffn_w4.txt): two slices beat one by 8 % at N = 64 and tie at
+// N = 256; four and eight, and 32-column tiles, lose at both.
+#define MOE_W4_DOWN_SLICES 2
+
+extern "C" int moe_ffn_w4_plan(int F, int splits) {
+  if (F < W4_G || F % W4_G) return 0;
+  const int nch = F / W4_G;
+  int S = splits > 0 ? splits : MOE_W4_DOWN_SLICES;
+  if (S > nch) {
+    if (splits > 0) return 0;
+    S = nch;
+  }
+  const int cps = (nch + S - 1) / S;
+  return (nch + cps - 1) / cps;
+}
+
+// gate_up_q int32 [E,2F,d/8], gate_up_s bf16 [E,2F,d/128], down_q int32
+// [E,d,F/8], down_s bf16 [E,d,F/128]; sched, h, out as in moe_ffn_bf16; y f32
+// [S, N*top_k, d] with S = moe_ffn_w4_plan(F, splits).
+extern "C" int moe_ffn_w4_bf16(const void* x, const void* gate_up_q,
+                               const void* gate_up_s, const void* down_q,
+                               const void* down_s, const float* weights,
+                               const int* idx, int* sched, void* h, float* y,
+                               void* out, long long N, int d, int F, int E,
+                               int top_k, int splits, hipStream_t stream) {
+  if (!moe_shape_ok(N, E, top_k) || d < W4_G || d % W4_G) return 1;
+  const int S = moe_ffn_w4_plan(F, splits);
+  if (S < 1) return 1;
+  const int cps = (F / W4_G + S - 1) / S;
+  const int max_tiles = moe_max_tiles(N, top_k, E);
+  const long long up_blocks = (long long)max_tiles * (F / 32);
+  const long long down_blocks = (long long)max_tiles * (d / 64) * S;
+  if (up_blocks >= (1ll << 31) || down_blocks >= (1ll << 31)) return 1;
+  int* slot_map = sched;
+  int* tile_expert = sched + (size_t)max_tiles * MOE_BM;
+  int* num_tiles = tile_expert + max_tiles;
+  const int P = (int)(N * top_k);
+  const long long plane = (long long)P * d;
+  const int* guq = (const int*)gate_up_q;
+  const int* dq = (const int*)down_q;
+  const unsigned short* gus = (const unsigned short*)gate_up_s;
+  const unsigned short* ds = (const unsigned short*)down_s;
+
+  hipLaunchKernelGGL(moe_align_kernel, dim3(1), dim3(MOE_ALIGN_NT), 0, stream,
+                     idx, P, E, slot_map, tile_expert, num_tiles);
+  hipLaunchKernelGGL((moe_gemm_w4_kernel<true>), dim3((unsigned)up_blocks),
+                     dim3(WAVE), 0, stream, (const short*)x, guq, gus,
+                     slot_map, tile_expert, num_tiles, (short*)h,
+                     (float*)nullptr, d, F, top_k, max_tiles, d / W4_G, 0ll);
+  hipLaunchKernelGGL((moe_gemm_w4_kernel<false>), dim3((unsigned)down_blocks),
+                     dim3(WAVE), 0, stream, (const short*)h, dq, ds, slot_map,
+                     tile_expert, num_tiles, (short*)nullptr, y, F, d, top_k,
+                     max_tiles, cps, plane);
+  const long long n4 = N * (d / 4);
+  int grid = (int)((n4 + 255) / 256 > 4096 ? 4096 : (n4 + 255) / 256);
+  if (S == 1)
+    hipLaunchKernelGGL(moe_combine_kernel, dim3(grid), dim3(256), 0, stream,
+                       (const float*)y, weights, (short*)out, n4, d / 4,
+                       top_k);
+  else
+    hipLaunchKernelGGL(moe_combine_planes_kernel, dim3(grid), dim3(256), 0,
+                       stream, (const float*)y, weights, (short*)out, n4,
+                       d / 4, top_k, S, plane);
   return 0;
 }

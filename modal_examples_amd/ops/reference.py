@@ -547,6 +547,31 @@ def dequantize_w4_ref(qweight, scales):
     return w.view(N, K)
 
 
+def quantize_w4_experts_ref(w):
+    """w [E, R, K] -> (q int32 [E, R, K/8], s bf16 [E, R, K/128]):
+    quantize_w4_ref over the flattened rows."""
+    E, R, K = w.shape
+    q, s = quantize_w4_ref(w.reshape(E * R, K))
+    return q.view(E, R, K // 8), s.view(E, R, K // W4_GROUP)
+
+
+def dequantize_w4_experts_ref(q, s):
+    """w_hat fp32 [E, R, K], exact (dequantize_w4_ref over the flattened
+    rows)."""
+    E, R = q.shape[:2]
+    return dequantize_w4_ref(q.reshape(E * R, -1),
+                             s.reshape(E * R, -1)).view(E, R, -1)
+
+
+def moe_ffn_w4_ref(x, gate_up_q, gate_up_s, down_q, down_s, weights, idx):
+    """moe_ffn_ref on the dequantized experts, which stay exact (fp32, or
+    fp64 beside an fp64 x).  Differentiable in x and the routing weights."""
+    wide = _wide(x).dtype
+    return moe_ffn_ref(x, dequantize_w4_experts_ref(gate_up_q, gate_up_s).to(wide),
+                       dequantize_w4_experts_ref(down_q, down_s).to(wide),
+                       weights, idx)
+
+
 def linear_w4_ref(x, qweight, scales):
     """x [..., K] . w_hat^T with w_hat cast to x's dtype (exact for fp32 and
     wider; one rounding per weight for bf16).  Differentiable in x."""

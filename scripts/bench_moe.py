@@ -13,7 +13,16 @@ over time against the measured HBM copy rate, the fused forward replayed
 from a captured graph, and (--e2e) decode tokens/s of an 8-layer cut of the
 serving example for loop+eager, fused+eager and fused+graph.
 
+--expert-dtype int4 adds the int4-expert lane (ops.moe_ffn_w4) on the same
+weights, quantized, to the same alternation: moe_ffn_w4_only, fused_w4,
+fused_w4_graph, and dequant_loop_w4, MoEFFN's prefill lane forced at every N
+(the crossover of the two lanes fixes MoEFFN.N_KERNEL).  Its bytes count
+0.52 B per weight (4 bits + one bf16 scale per 128).  --w4-sweep also times
+ops.moe_ffn_w4 with the down GEMM's K forced into 1, 2, 4 and 8 slices,
+beside the shipped rule.
+
 Usage: python scripts/bench_moe.py [--tokens 64 256 4096] [--e2e]
+                                   [--expert-dtype int4] [--w4-sweep]
 """
 import argparse
 import os
@@ -58,16 +67,70 @@ def time_arms(arms):
             for n, s in samples.items()}
 
 
-def ffn_bytes(N, dim, ffn, k, touched, slots):
+W4_BYTES = 0.5 + 2 / 128   # per weight: a nibble + a bf16 scale per 128
+W4_DOWN_SLICES = 2         # csrc/moe.hip's rule: min(2, ffn / 128)
+W4_SWEEP = (1, 2, 4, 8)    # K slices of the down GEMM, forced
+
+
+def ffn_bytes(N, dim, ffn, k, touched, slots, wbytes=2, planes=1):
     """Algorithmic bytes of ops.moe_ffn: every touched expert's weights
     once, x and out, the bf16 h and fp32 y workspaces written and read."""
-    weights = touched * 3 * ffn * dim * 2
+    weights = touched * 3 * ffn * dim * wbytes
     act = 2 * N * dim * 2
-    work = 2 * slots * ffn * 2 + 2 * N * k * dim * 4
-    return weights, act + work
+    work = 2 * slots * ffn * 2 + 2 * planes * N * k * dim * 4
+    return int(weights), act + work
 
 
-def bench_ffn(N, dim, ffn, E, k, out):
+def _capture(module, static_x):
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        for _ in range(2):
+            module(static_x)
+    torch.cuda.current_stream().wait_stream(side)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        module(static_x)
+    return graph
+
+
+def w4_arms(loop, x, flat, w, idx, sweep):
+    """The int4 arms over loop's weights, quantized; (arms, graph)."""
+    from modal_examples_amd.models.llama.model import MoEFFN
+    from modal_examples_amd.ops import functional as OF
+    from modal_examples_amd.ops._build import get_ext
+
+    E, _, dim = loop.gate_up.shape
+    ffn, k = loop.down.shape[2], loop.top_k
+    packed = (OF.quantize_w4_experts(loop.gate_up.data)
+              + OF.quantize_w4_experts(loop.down.data))
+    mods = []
+    for _ in range(2):
+        with torch.device("meta"):
+            m = MoEFFN(dim, ffn, E, k, impl="fused", expert_dtype="int4")
+        m.router = loop.router
+        m.gate_up_q, m.gate_up_s, m.down_q, m.down_s = packed
+        mods.append(m)
+    fused_w4, prefill_w4 = mods
+    fused_w4.N_KERNEL = 1 << 30   # this arm is the kernel lane at every N
+    prefill_w4.N_KERNEL = 0       # and this one the dequantize-and-loop lane
+    graph = _capture(fused_w4, x.clone())
+    arms = {
+        "fused_w4": lambda: fused_w4(x),
+        "fused_w4_graph": graph.replay,
+        "moe_ffn_w4_only": lambda: OF.moe_ffn_w4(flat, *packed, w, idx),
+        "dequant_loop_w4": lambda: prefill_w4(x),
+    }
+    if sweep:
+        ext = get_ext(required=True)
+        for s in W4_SWEEP:
+            if s <= ffn // 128:
+                arms[f"w4_only[s{s}]"] = (
+                    lambda s=s: ext.moe_ffn_w4(flat, *packed, w, idx, s))
+    return arms, graph, fused_w4
+
+
+def bench_ffn(N, dim, ffn, E, k, out, expert_dtype="bf16", sweep=False):
     from modal_examples_amd.models.llama.model import MoEFFN
     from modal_examples_amd.ops import functional as OF
 
@@ -98,8 +161,13 @@ def bench_ffn(N, dim, ffn, E, k, out):
             "moe_ffn_only": lambda: OF.moe_ffn(flat, loop.gate_up, loop.down,
                                                w, idx),
         }
+        if expert_dtype == "int4":
+            more, graph_w4, fused_w4 = w4_arms(loop, x, flat, w, idx, sweep)
+            arms.update(more)
         res = time_arms(arms)
         diff = (fused(x).float() - loop(x).float()).abs().max().item()
+        if expert_dtype == "int4":
+            diff_w4 = (fused_w4(x).float() - fused(x).float()).abs().max().item()
     counts = torch.bincount(idx.flatten().long(), minlength=E)
     touched = int((counts > 0).sum())
     slots = int(((counts + 31) // 32 * 32).sum())
@@ -116,19 +184,40 @@ def bench_ffn(N, dim, ffn, E, k, out):
         f"{(wb + ob) / t / 1e12 / HBM_COPY_TBS:.0%} of the {HBM_COPY_TBS} TB/s"
         f" copy rate (memory bound: {2 * 3 * N * k * dim * ffn / t / 1e12:.0f}"
         f" TFLOP/s is far below the MFMA peak)")
+    if expert_dtype == "int4":
+        a, b = res["moe_ffn_w4_only"], res["moe_ffn_only"]
+        t4 = a[0] * 1e-6
+        planes = min(W4_DOWN_SLICES, ffn // 128)
+        wb4, ob4 = ffn_bytes(N, dim, ffn, k, touched, slots, W4_BYTES, planes)
+        out(f"N={N:5d} int4/bf16 moe_ffn_only = {a[0] / b[0]:.3f} "
+            f"({b[0] / a[0]:.2f}x; spreads: int4 {a[2] - a[1]:.1f} us, bf16 "
+            f"{b[2] - b[1]:.1f} us, gap {b[0] - a[0]:.1f} us)   "
+            f"max|fused_w4-fused| = {diff_w4:.3e} (quantization included)")
+        out(f"N={N:5d} moe_ffn_w4_only: {wb4 / 1e6:.1f} MB weights + "
+            f"{ob4 / 1e6:.1f} MB activations/workspaces -> "
+            f"{(wb4 + ob4) / t4 / 1e12:.2f} TB/s algorithmic = "
+            f"{(wb4 + ob4) / t4 / 1e12 / HBM_COPY_TBS:.0%} of the "
+            f"{HBM_COPY_TBS} TB/s copy rate")
+        out(f"N={N:5d} crossover: kernel lane {res['fused_w4'][0]:.1f} us, "
+            f"dequantize-and-loop lane {res['dequant_loop_w4'][0]:.1f} us")
+        del graph_w4
     del graph
 
 
-def bench_e2e(out, layers=8, batch=64, steps=24):
+def bench_e2e(out, layers=8, batch=64, steps=24, expert_dtype="bf16"):
     from modal_examples_amd.models.llama.engine import LlamaEngine
     from modal_examples_amd.models.llama.model import LlamaConfig
 
-    for impl, graph in (("loop", False), ("fused", False), ("fused", True)):
+    lanes = [("loop", False, "bf16"), ("fused", False, "bf16"),
+             ("fused", True, "bf16")]
+    if expert_dtype == "int4":
+        lanes += [("fused", False, "int4"), ("fused", True, "int4")]
+    for impl, graph, edt in lanes:
         torch.manual_seed(0)
         cfg = LlamaConfig(n_experts=8, ffn_dim=4096, n_layers=layers)
         eng = LlamaEngine(cfg, device="cuda", dtype=torch.bfloat16,
                           moe_impl=impl, use_graph=graph, kv_blocks=4096,
-                          max_batch=batch, eos_id=-1)
+                          max_batch=batch, eos_id=-1, expert_dtype=edt)
         for i in range(batch):
             eng.add_request([1 + i, 7, 9, 11], max_new_tokens=steps + 16,
                             temperature=0.0)
@@ -144,7 +233,7 @@ def bench_e2e(out, layers=8, batch=64, steps=24):
         dt = time.perf_counter() - t0
         n1 = sum(len(r.out_tokens) for r in eng.running)
         out(f"e2e {layers} layers batch {batch}: moe_impl={impl:5s} "
-            f"graph={graph!s:5s} {(n1 - n0) / dt:9.1f} tok/s "
+            f"experts={edt:4s} graph={graph!s:5s} {(n1 - n0) / dt:9.1f} tok/s "
             f"({dt / steps * 1e3:.2f} ms/step over {steps} steps)")
         eng.close()
         del eng
@@ -159,6 +248,8 @@ def main():
     ap.add_argument("--experts", type=int, default=8)
     ap.add_argument("--top-k", type=int, default=2)
     ap.add_argument("--e2e", action="store_true")
+    ap.add_argument("--expert-dtype", choices=("bf16", "int4"), default="bf16")
+    ap.add_argument("--w4-sweep", action="store_true")
     ap.add_argument("--out", default=None, help="also append the lines here")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -173,9 +264,10 @@ def main():
     out(f"# bench_moe: dim={a.dim} ffn={a.ffn} E={a.experts} k={a.top_k} bf16,"
         f" {torch.cuda.get_device_name(0)}")
     for N in a.tokens:
-        bench_ffn(N, a.dim, a.ffn, a.experts, a.top_k, out)
+        bench_ffn(N, a.dim, a.ffn, a.experts, a.top_k, out, a.expert_dtype,
+                  a.w4_sweep)
     if a.e2e:
-        bench_e2e(out)
+        bench_e2e(out, expert_dtype=a.expert_dtype)
 
 
 if __name__ == "__main__":

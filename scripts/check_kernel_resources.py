@@ -50,10 +50,18 @@ OCCUPANCY_FLOORS = {
     "moe_combine_kernel": 8,
     # w4_gemm_kernel: two register sets of a 128-deep chunk (x fragments,
     # packed words, scales) beside 32 accumulators and the group's 48 partial
-    # sums; built for two waves per SIMD (242 VGPRs), the second wave hides
+    # sums; built for two waves per SIMD (249 VGPRs), the second wave hides
     # a chunk's load latency
     "w4_gemm_kernel": 2,
     "w4_reduce_kernel": 8,
+    # moe_gemm_w4_kernel<UP>: w4_gemm_kernel's register picture (two sets of
+    # a 128-deep group, 32 accumulators, 48 partial sums) plus the slot-map
+    # gather; built for two waves per SIMD (248 / 232 VGPRs), which is what
+    # hides a group's load latency now that a wave streams a quarter of the
+    # bf16 kernel's bytes
+    "moe_gemm_w4_kernelILb1E": 2,    # up GEMM
+    "moe_gemm_w4_kernelILb0E": 2,    # down GEMM, one K slice per wave
+    "moe_combine_planes_kernel": 8,
 }
 
 
