@@ -20,6 +20,7 @@ Sized for 288 GB HBM3E: KV pool defaults to 60% of free memory after weights
 from __future__ import annotations
 
 import dataclasses
+import itertools
 import time
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional
@@ -81,6 +82,7 @@ class LlamaEngine:
                  prefix_cache: bool = False,
                  gpu_mem_util: float = 0.6,
                  prefill_attn: str = "decode",
+                 spec_attn: str = "rows",
                  moe_impl: Optional[str] = None,
                  weight_dtype: str = "bf16",
                  expert_dtype: Optional[str] = None):
@@ -118,6 +120,16 @@ class LlamaEngine:
         ops.paged_prefill once per layer on the request's one block-table
         row (csrc/attention_prefill_paged.hip).  Monolithic prefill,
         decode and speculative verification are the same under both.
+
+        spec_attn: the attention kernel of the speculative verify step.
+        "rows" (default) turns a request's k+1 draft positions into k+1
+        rows of the paged decode kernel, each sweeping the request's whole
+        cache; "packed" calls ops.paged_decode_packed on one table row per
+        request (csrc/attention_decode_packed.hip): the k+1 positions times
+        the G heads of a kv-head group share one MFMA tile and one cache
+        sweep.  It needs (spec_tokens + 1) * G <= 32 with G the local
+        Hq/Hkv (ValueError otherwise).  Every other lane is the same under
+        both.
 
         moe_impl: the forward of an MoE config's expert FFN (MoEFFN):
         "loop", the host loop over active experts, or "fused", the
@@ -195,6 +207,16 @@ class LlamaEngine:
             raise ValueError(f"prefill_attn must be 'decode' or 'paged', got "
                              f"{prefill_attn!r}")
         self.prefill_attn = prefill_attn
+        if spec_attn not in ("rows", "packed"):
+            raise ValueError(f"spec_attn must be 'rows' or 'packed', got "
+                             f"{spec_attn!r}")
+        # Hq/Hkv of a rank's shard is the config's: tp splits both alike
+        group = self.cfg.n_heads // self.cfg.n_kv_heads
+        if spec_attn == "packed" and (spec_tokens + 1) * group > 32:
+            raise ValueError(
+                f"spec_attn='packed' needs (spec_tokens + 1) * (Hq/Hkv) <= "
+                f"32, got spec_tokens={spec_tokens} Hq/Hkv={group}")
+        self.spec_attn = spec_attn
         self.prefilling: List[Request] = []  # long prompts mid-chunk
         self.prefix_cache = prefix_cache
         self._pc_map: Dict = {}    # chain-hash -> block id
@@ -889,7 +911,6 @@ class LlamaEngine:
         toks = torch.tensor(rows_tok, dtype=torch.long, device=dev)
         pos = torch.tensor(rows_pos, dtype=torch.int32, device=dev)
         bt = self.bt_d[torch.tensor(rows_slot, dtype=torch.long, device=dev)]
-        lens = pos + 1
         blks = bt.gather(1, (pos // BLOCK).long().unsqueeze(1))[:, 0].long()
         offs = (pos % BLOCK).long()
 
@@ -898,9 +919,30 @@ class LlamaEngine:
             self.cache_k[li][blks, :, offs] = k[:, 0].to(self.cache_k.dtype)
             self.cache_v[li][blks, :, offs] = v[:, 0].to(self.cache_v.dtype)
 
-        def kv_attend(li, q):
-            return OF.paged_decode(q, self.cache_k[li], self.cache_v[li],
-                                   bt, lens, BLOCK)
+        if self.spec_attn == "packed":
+            # one table row, one seq_lens entry and one cu_q step per
+            # REQUEST: its rows are a run of new tokens ending at the last
+            # draft position (decode_step appends a layer's K/V before it
+            # attends, so the cache holds them as the op expects)
+            run = [len(drafts) + 1 for _, _, drafts in plan]
+            bt_req = self.bt_d[torch.tensor([r.slot for r, _, _ in plan],
+                                            dtype=torch.long, device=dev)]
+            cu_q = torch.tensor([0] + list(itertools.accumulate(run)),
+                                dtype=torch.int32, device=dev)
+            seq_lens = torch.tensor(
+                [r.pos + n for (r, _, _), n in zip(plan, run)],
+                dtype=torch.int32, device=dev)
+
+            def kv_attend(li, q):
+                return OF.paged_decode_packed(
+                    q, self.cache_k[li], self.cache_v[li], bt_req, cu_q,
+                    seq_lens, BLOCK, max_q_len=self.spec_tokens + 1)
+        else:
+            lens = pos + 1
+
+            def kv_attend(li, q):
+                return OF.paged_decode(q, self.cache_k[li], self.cache_v[li],
+                                       bt, lens, BLOCK)
 
         logits = self.model.decode_step(toks, pos, kv_append, kv_attend)
         row_reqs = [None] * len(rows_tok)

@@ -23,6 +23,7 @@ HIP_SOURCES = [
     "attention_fwd32.hip",
     "attention_bwd.hip",
     "attention_decode.hip",
+    "attention_decode_packed.hip",
     "attention_prefill_paged.hip",
     "norms.hip",
     "elementwise.hip",
@@ -32,6 +33,16 @@ HIP_SOURCES = [
     "moe.hip",
     "linear_w4.hip",
 ]
+
+# Per-source compiler flags beyond `common`; scripts/check_kernel_resources.py
+# audits each source with the same ones.  The packed decode kernel is built
+# without the packed fp32 VALU forms, like the int4 kernels (w4_mma.h) — as a
+# flag, because the function attribute used there would keep the shared
+# attention_mfma32.h helpers from being inlined (see the kernel's comment).
+EXTRA_FLAGS = {
+    "attention_decode_packed.hip": ["-Xclang", "-target-feature", "-Xclang",
+                                    "-packed-fp32-ops"],
+}
 
 
 def _run(cmd):
@@ -86,7 +97,8 @@ def build(verbose: bool = False, force: bool = False) -> Path:
         if force or _mtime(op) < max(_mtime(sp), hdr_m):
             if verbose:
                 print(f"[ops] hipcc -c {src}", flush=True)
-            _run([hipcc, *common, "-c", str(sp), "-o", str(op)])
+            _run([hipcc, *common, *EXTRA_FLAGS.get(src, []), "-c", str(sp),
+                  "-o", str(op)])
             relink = True
         objs.append(str(op))
 

@@ -248,6 +248,16 @@ __global__ __launch_bounds__(256) void decode_merge_kernel(
   }
 }
 
+// The merge alone, for other kernels that write the [rows, Hq, splits, D+2]
+// workspace (attention_decode_packed.hip): o [rows, Hq, D] bf16.
+extern "C" void decode_merge_bf16(const float* ws, void* o, long long rows,
+                                  int Hq, int D, int splits,
+                                  hipStream_t stream) {
+  hipLaunchKernelGGL(decode_merge_kernel, dim3((unsigned)(rows * Hq)),
+                     dim3(256), 0, stream, ws, (short*)o, (int)rows, Hq, D,
+                     splits);
+}
+
 // Returns 0 once the kernels are launched, non-zero (nothing launched) for an
 // unsupported configuration: D must be 64 or 128, Hq a multiple of Hkv and
 // the GQA group Hq/Hkv at most MAX_G.

@@ -52,6 +52,12 @@ DEV_INLINE bf16x8 row_frag(const short* tile, int row, int hi5, int c) {
                           tile_swz(row, (c * 16 + hi5 * 8) * 2));
 }
 
+// Store of one 16 B chunk (8 bf16 at column c8*8) of a row of the same tile.
+template <int KROW>
+DEV_INLINE void row_store(short* tile, int row, int c8, bf16x8 v) {
+  *(bf16x8*)((char*)tile + row * (KROW * 2) + tile_swz(row, c8 * 16)) = v;
+}
+
 // Transposed read of the same tile as the A operand T^T: lane holds
 // T[c*16 + hi5*8 + j][dt*32 + l31].  ds_read_b64_tr_b16 semantics, measured
 // (scripts/probe_tr16.cpp; the documented behaviour is wrong on this part):
@@ -113,6 +119,27 @@ DEV_INLINE void lane_pair(float x, float& lo, float& hi) {
   int r0 = r[0], r1 = r[1];
   lo = __builtin_bit_cast(float, r0);
   hi = __builtin_bit_cast(float, r1);
+}
+
+typedef __attribute__((ext_vector_type(2))) unsigned int u32x2p;
+
+// 8 OCP e4m3 (two dwords) -> 8 bf16: the HW converter widens to f32, whose
+// high half is the bf16 of the same value (3 mantissa bits, nothing dropped).
+DEV_INLINE bf16x8 fp8x8_to_bf16x8(u32x2p w) {
+  union {
+    unsigned u[4];
+    bf16x8 v;
+  } r;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[h], false);  // bytes 0,1
+    f32x2 hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[h], true);   // bytes 2,3
+    r.u[2 * h] = (__float_as_uint(lo[0]) >> 16) |
+                 (__float_as_uint(lo[1]) & 0xffff0000u);
+    r.u[2 * h + 1] = (__float_as_uint(hi[0]) >> 16) |
+                     (__float_as_uint(hi[1]) & 0xffff0000u);
+  }
+  return r.v;
 }
 
 // Two-tile staging, global -> registers -> swizzled LDS, split so the loads

@@ -25,27 +25,6 @@
 
 #define PP_NWAVES 4
 
-typedef __attribute__((ext_vector_type(2))) unsigned int u32x2p;
-
-// 8 OCP e4m3 (two dwords) -> 8 bf16: the HW converter widens to f32, whose
-// high half is the bf16 of the same value (3 mantissa bits, nothing dropped).
-DEV_INLINE bf16x8 fp8x8_to_bf16x8(u32x2p w) {
-  union {
-    unsigned u[4];
-    bf16x8 v;
-  } r;
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    f32x2 lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[h], false);  // bytes 0,1
-    f32x2 hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)w[h], true);   // bytes 2,3
-    r.u[2 * h] = (__float_as_uint(lo[0]) >> 16) |
-                 (__float_as_uint(lo[1]) & 0xffff0000u);
-    r.u[2 * h + 1] = (__float_as_uint(hi[0]) >> 16) |
-                     (__float_as_uint(hi[1]) & 0xffff0000u);
-  }
-  return r.v;
-}
-
 // The waves-per-SIMD requests are the forward kernel's occupancies (3 at
 // D=64, 2 at D=128).  Without the 2, the D=128 fp8 instance is allocated 258
 // registers — two past the 2-wave edge — and runs at 1 wave/SIMD; with it

@@ -29,6 +29,13 @@ int paged_decode_bf16(const void*, const void*, const void*, const int*,
 int paged_prefill_bf16(const void*, const void*, const void*, const int*,
                        const int*, const int*, void*, int, int, int, int, int,
                        int, int, float, int, hipStream_t);
+// paged_decode_packed_splits: the flash-decoding split count of a call, 0
+// for a forced count the kernel does not take
+int paged_decode_packed_splits(long long, int, long long, int);
+int paged_decode_packed_bf16(const void*, const void*, const void*, const int*,
+                             const int*, const int*, void*, float*, long long,
+                             int, int, int, int, int, int, int, int, float,
+                             int, hipStream_t);
 void groupnorm_silu_bf16(const void*, void*, float*, const float*,
                          const float*, int, int, long long, int, float, int,
                          hipStream_t);
@@ -360,6 +367,94 @@ torch::Tensor paged_prefill(torch::Tensor q, torch::Tensor kc, torch::Tensor vc,
               "kernel (head_dim must be 64 or 128, Hq a multiple of Hkv, B "
               "and Hq at most 65535; got D=", D, " Hq=", Hq, " Hkv=", Hkv,
               " B=", B, ")");
+  return o;
+}
+
+// paged_prefill's semantics for runs of at most 32 / (Hq/Hkv) new tokens per
+// sequence, on the packed decode kernel (csrc/attention_decode_packed.hip):
+// one KV sweep per (sequence, kv head) serves every new token and every head
+// of the group.  Every check raises before anything is launched; the
+// preconditions only the device knows are paged_prefill's.  splits = 0
+// takes the kernel's flash-decoding rule (shapes only, so the op captures
+// into a graph); a positive value forces that many (tests and benchmarks,
+// the public op never passes it).
+torch::Tensor paged_decode_packed(torch::Tensor q, torch::Tensor kc,
+                                  torch::Tensor vc, torch::Tensor block_table,
+                                  torch::Tensor cu_q, torch::Tensor seq_lens,
+                                  int64_t block_size, double scale,
+                                  int64_t max_q_len, int64_t splits) {
+  const char* op = "paged_decode_packed";
+  check_bf16(q, "q");
+  TORCH_CHECK(q.dim() == 3, op, ": q must be [R,Hq,D]");
+  const bool kv_fp8 = kc.scalar_type() == torch::kFloat8_e4m3fn;
+  TORCH_CHECK(kv_fp8 || kc.scalar_type() == torch::kBFloat16,
+              "k_cache must be bf16 or float8_e4m3fn");
+  TORCH_CHECK(vc.scalar_type() == kc.scalar_type(), "kv cache dtype mismatch");
+  TORCH_CHECK(kc.dim() == 4 && vc.sizes() == kc.sizes() &&
+                  kc.is_contiguous() && vc.is_contiguous(),
+              op, ": k_cache/v_cache must be contiguous "
+              "[blocks,Hkv,block_size,D] of one shape");
+  const int64_t R = q.size(0);
+  const int Hq = q.size(1), D = q.size(2), Hkv = kc.size(1);
+  TORCH_CHECK(D == 64 || D == 128, op, ": unsupported head_dim ", D,
+              " (supported: 64, 128)");
+  TORCH_CHECK(kc.size(3) == D, op, ": k_cache head_dim ", kc.size(3),
+              " != q head_dim ", D);
+  TORCH_CHECK(Hkv > 0 && Hq % Hkv == 0, "GQA requires Hq % Hkv == 0, got Hq=",
+              Hq, " Hkv=", Hkv);
+  const int G = Hq / Hkv;
+  TORCH_CHECK(G <= 8, op, ": unsupported GQA group Hq/Hkv = ", G,
+              " (supported: 1..8)");
+  TORCH_CHECK(block_size > 0 && kc.size(2) == block_size, op,
+              ": block_size must be positive and the cache's third dim, got "
+              "block_size=", block_size, " cache ", kc.sizes());
+  TORCH_CHECK(seq_lens.scalar_type() == torch::kInt32 && seq_lens.dim() == 1 &&
+                  seq_lens.is_contiguous(),
+              op, ": seq_lens must be int32 [B] contiguous");
+  const int64_t B = seq_lens.size(0);
+  TORCH_CHECK(block_table.scalar_type() == torch::kInt32 &&
+                  block_table.dim() == 2 && block_table.size(0) == B &&
+                  block_table.size(1) >= 1 && block_table.is_contiguous(),
+              op, ": block_table must be int32 [B=", B,
+              ", max_blocks] contiguous, got ", block_table.sizes());
+  TORCH_CHECK(cu_q.scalar_type() == torch::kInt32 && cu_q.dim() == 1 &&
+                  cu_q.size(0) == B + 1 && cu_q.is_contiguous(),
+              op, ": cu_q must be int32 [B+1=", B + 1, "], got ",
+              cu_q.sizes());
+  for (const torch::Tensor* t : {&kc, &vc, &block_table, &cu_q, &seq_lens})
+    TORCH_CHECK(t->device() == q.device(), op,
+                ": all tensors must be on q's device");
+  auto o = torch::empty_like(q);
+  if (R == 0) return o;  // nothing to attend: max_q_len=None arrives as R = 0
+  TORCH_CHECK(max_q_len >= 1, op, ": max_q_len must be at least 1, got ",
+              max_q_len);
+  TORCH_CHECK(max_q_len * G <= 32, op, ": max_q_len * (Hq/Hkv) must be at "
+              "most 32 (one packed MFMA tile), got max_q_len=", max_q_len,
+              " Hq/Hkv=", G);
+  TORCH_CHECK(B >= 1 && B <= 65535, op, ": ", R, " query rows over B=", B,
+              " sequences (supported: 1..65535)");
+  const int64_t max_blocks = block_table.size(1);
+  const int ns = paged_decode_packed_splits(B, Hkv, max_blocks * block_size,
+                                            (int)std::min<int64_t>(
+                                                std::max<int64_t>(splits, -1),
+                                                1 << 20));
+  TORCH_CHECK(ns >= 1, op, ": splits must be 0 (the kernel's rule) or 1..64, "
+              "got ", splits);
+  torch::Tensor ws;
+  float* ws_ptr = nullptr;
+  if (ns > 1) {
+    ws = torch::empty({R * Hq * ns * (D + 2)},
+                      q.options().dtype(torch::kFloat32));
+    ws_ptr = ws.data_ptr<float>();
+  }
+  int rc = paged_decode_packed_bf16(
+      q.data_ptr(), kc.data_ptr(), vc.data_ptr(), block_table.data_ptr<int>(),
+      cu_q.data_ptr<int>(), seq_lens.data_ptr<int>(), o.data_ptr(), ws_ptr, R,
+      (int)B, Hq, Hkv, D, (int)block_size, (int)max_blocks, (int)max_q_len,
+      ns, (float)scale, kv_fp8 ? 1 : 0, cur_stream());
+  TORCH_CHECK(rc == 0, op, ": configuration not supported by the kernel "
+              "(got D=", D, " Hq=", Hq, " Hkv=", Hkv, " B=", B,
+              " max_q_len=", max_q_len, " splits=", ns, ")");
   return o;
 }
 
@@ -1166,6 +1261,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("paged_prefill", &paged_prefill,
         "paged KV prefill attention: ragged causal chunks over a cached "
         "prefix (K6)");
+  m.def("paged_decode_packed", &paged_decode_packed,
+        "packed multi-token paged decode: GQA heads x new tokens on one MFMA "
+        "tile, one KV sweep per (sequence, kv head) (K6)",
+        py::arg("q"), py::arg("k_cache"), py::arg("v_cache"),
+        py::arg("block_table"), py::arg("cu_q"), py::arg("seq_lens"),
+        py::arg("block_size"), py::arg("scale"), py::arg("max_q_len"),
+        py::arg("splits") = 0);
   m.def("groupnorm_silu", &groupnorm_silu);
   m.def("groupnorm_silu_nhwc", &groupnorm_silu_nhwc,
         "GroupNorm(+SiLU) of NCHW x, written as [N, H*W, C]");

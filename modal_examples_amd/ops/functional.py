@@ -215,6 +215,46 @@ def paged_prefill(q, k_cache, v_cache, block_table, cu_q, seq_lens,
                              q.shape[0] if max_q_len is None else max_q_len)
 
 
+def paged_decode_packed(q, k_cache, v_cache, block_table, cu_q, seq_lens,
+                        block_size: int, scale: Optional[float] = None,
+                        max_q_len: Optional[int] = None):
+    """`paged_prefill` for SHORT runs of new tokens — the verify step of
+    speculative decoding (K6).  The T new tokens of a sequence times the
+    G = Hq/Hkv heads of a kv-head group share one 32-wide MFMA tile, so one
+    sweep of the sequence's KV cache per kv head serves all of them
+    (csrc/attention_decode_packed.hip), with flash-decoding splits at small
+    batch.
+
+    Arguments and return value are `paged_prefill`'s.  max_q_len bounds the
+    longest run (None means R = q.shape[0]) and max_q_len * G must not
+    exceed 32 (ValueError); G is at most 8."""
+    if block_table is None:
+        raise ValueError("paged_decode_packed needs a block_table (there is "
+                         "no contiguous-cache mode)")
+    R, Hq = q.shape[0], q.shape[1]
+    Hkv = k_cache.shape[1]
+    mq = R if max_q_len is None else max_q_len
+    if Hkv > 0 and Hq % Hkv == 0 and mq * (Hq // Hkv) > 32:
+        raise ValueError(
+            f"paged_decode_packed: max_q_len * (Hq/Hkv) = {mq} * "
+            f"{Hq // Hkv} exceeds the 32 rows of the packed tile")
+    scale = scale if scale is not None else 1.0 / math.sqrt(q.shape[-1])
+    ext = _ext_for(q)
+    if ext is None:
+        if k_cache.dtype not in (torch.float32, torch.float64, torch.bfloat16,
+                                 torch.float16):
+            k_cache = k_cache.to(torch.float32)
+            v_cache = v_cache.to(torch.float32)
+        return ref.paged_prefill_ref(q, k_cache, v_cache, block_table, cu_q,
+                                     seq_lens, block_size, scale)
+    # .contiguous() also materializes expand()ed (stride-0) block tables
+    return ext.paged_decode_packed(q.contiguous(), k_cache, v_cache,
+                                   block_table.contiguous(),
+                                   cu_q.int().contiguous(),
+                                   seq_lens.int().contiguous(), block_size,
+                                   scale, mq)
+
+
 def groupnorm_silu(x, gamma, beta, groups: int = 32, eps: float = 1e-5,
                    do_silu: bool = True, out_nhwc: bool = False):
     """GroupNorm(+SiLU) of x [N,C,H,W].  out_nhwc=True returns the result as

@@ -196,6 +196,79 @@ def bench_paged_prefill(results):
                 print(name, json.dumps(r), flush=True)
 
 
+def bench_paged_decode_packed(results):
+    """The verify step of speculative decoding at Llama-3-8B heads (Hq 32,
+    Hkv 8, D 128, block 16, shuffled tables): T new tokens per sequence on
+    F.paged_decode_packed against the lane it replaces, F.paged_decode over
+    B*T expanded rows (table row repeated, lens = ctx-T+1 .. ctx), and for
+    scale F.paged_decode at T = 1 on the same cache: one KV sweep, the floor.
+    The three are timed in one process, alternating.  Outputs of the two
+    lanes are compared at every timed shape (each is held to its bound of
+    the truth by the tests, so to twice that of each other).  kv_GBps is the
+    cache's K+V bytes once over the packed time."""
+    Hq, Hkv, D, bs = 32, 8, 128, 16
+    g = torch.Generator(device="cuda").manual_seed(0)
+
+    def randn(*shape):
+        return torch.randn(*shape, device="cuda", generator=g)
+
+    for fp8 in (False, True):
+        cdt = torch.float8_e4m3fn if fp8 else torch.bfloat16
+        amp = 0.5 if fp8 else 1.0
+        tol = 6e-2 if fp8 else 4e-2
+        for B in (1, 8, 64):
+            for ctx in (2048, 8192, 32768):
+                per = ctx // bs
+                # filled in slices: one randn of the B=64, 32k cache would
+                # hold 17 GB of fp32
+                kc = torch.empty(B * per, Hkv, bs, D, device="cuda", dtype=cdt)
+                vc = torch.empty_like(kc)
+                for c in (kc, vc):
+                    for lo in range(0, B * per, 4096):
+                        n = min(4096, B * per - lo)
+                        c[lo:lo + n] = (randn(n, Hkv, bs, D) * amp).to(cdt)
+                bt = torch.randperm(B * per, device="cuda",
+                                    generator=g).int().view(B, per)
+                full = torch.full((B,), ctx, dtype=torch.int32, device="cuda")
+                q1 = randn(B, Hq, D).to(torch.bfloat16)
+                for T in (2, 5, 8):
+                    q = randn(B * T, Hq, D).to(torch.bfloat16)
+                    cu = torch.arange(0, B * T + 1, T, dtype=torch.int32,
+                                      device="cuda")
+                    btx = bt.repeat_interleave(T, 0)
+                    lens = (ctx - T + 1 + torch.arange(
+                        T, dtype=torch.int32, device="cuda")).repeat(B)
+
+                    def packed():
+                        return F.paged_decode_packed(q, kc, vc, bt, cu, full,
+                                                     bs, max_q_len=T)
+
+                    def rows():
+                        return F.paged_decode(q, kc, vc, btx, lens, bs)
+
+                    def floor():
+                        return F.paged_decode(q1, kc, vc, bt, full, bs)
+
+                    a, b = packed().float(), rows().float()
+                    diff = (a - b).abs()
+                    ts = _alternate([packed, rows, floor])
+                    gb = 2 * kc.numel() * kc.element_size() / 1e9
+                    r = {"packed_ms": round(ts[0] * 1e3, 4),
+                         "rows_ms": round(ts[1] * 1e3, 4),
+                         "t1_floor_ms": round(ts[2] * 1e3, 4),
+                         "packed_over_rows": round(ts[0] / ts[1], 3),
+                         "packed_over_floor": round(ts[0] / ts[2], 3),
+                         "kv_GBps": round(gb / ts[0], 0),
+                         "max_abs_diff": round(float(diff.max()), 5),
+                         "outputs_agree": bool(
+                             (diff <= tol + tol * b.abs()).all())}
+                    name = (f"paged_decode_packed/{'fp8' if fp8 else 'bf16'}"
+                            f"_b{B}_s{ctx}_t{T}")
+                    results[name] = r
+                    print(name, json.dumps(r), flush=True)
+                del kc, vc
+
+
 def bench_memory_ops(results):
     x = torch.randn(16, 1280, 64, 64, device="cuda", dtype=torch.bfloat16)
     g = torch.randn(1280, device="cuda")
@@ -351,13 +424,15 @@ def main():
     ap.add_argument("--out", default="")
     ap.add_argument("--only", default="",
                     help="comma-separated groups: attention, attention_bwd, "
-                         "decode, paged_prefill, memory_ops, sdxl_glue, "
+                         "decode, paged_prefill, paged_decode_packed, "
+                         "memory_ops, sdxl_glue, "
                          "gemm_reference (default: all)")
     args = ap.parse_args()
     assert torch.cuda.is_available()
     groups = {"attention": bench_attention,
               "attention_bwd": bench_attention_bwd,
               "decode": bench_decode, "paged_prefill": bench_paged_prefill,
+              "paged_decode_packed": bench_paged_decode_packed,
               "memory_ops": bench_memory_ops,
               "sdxl_glue": bench_sdxl_glue,
               "gemm_reference": bench_gemm_reference}

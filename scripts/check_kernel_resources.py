@@ -15,7 +15,10 @@ import subprocess
 import sys
 from pathlib import Path
 
-CSRC = Path(__file__).resolve().parent.parent / "modal_examples_amd" / "ops" / "csrc"
+REPO = Path(__file__).resolve().parent.parent
+CSRC = REPO / "modal_examples_amd" / "ops" / "csrc"
+sys.path.insert(0, str(REPO))
+from modal_examples_amd.ops._build import EXTRA_FLAGS  # noqa: E402
 
 # kernel-name substring -> minimum waves/SIMD (from the shipped builds)
 OCCUPANCY_FLOORS = {
@@ -31,6 +34,11 @@ OCCUPANCY_FLOORS = {
     "paged_prefill_kernelILi64E": 3,   # bf16 and fp8 cache, the forward's 3
     "paged_prefill_kernelILi128E": 2,  # bf16 and fp8 cache, the forward's 2
     "decode_kernel": 2,
+    # paged_decode_packed_kernel<D, FP8>: 64 accumulators, 32 Q-fragment and
+    # up to 64 prefetch registers at D=128; two workgroups per CU are what
+    # covers a wave's staging and MFMA phases
+    "paged_decode_packed_kernelILi64E": 3,
+    "paged_decode_packed_kernelILi128E": 2,
     # conv3x3_kernel<UP, GN, RPW=2>: 64 accumulators + a chunk of staged
     # loads in flight must stay within 168 registers
     "conv3x3_kernelILb0ELb0ELi2E": 3,
@@ -67,8 +75,10 @@ OCCUPANCY_FLOORS = {
 
 def audit(path: Path) -> dict:
     r = subprocess.run(
-        ["hipcc", "--offload-arch=gfx950", "-O3", "-c", str(path),
-         "-o", "/dev/null", "-Rpass-analysis=kernel-resource-usage"],
+        ["hipcc", "--offload-arch=gfx950", "-O3",
+         *EXTRA_FLAGS.get(path.name, []),  # the flags the build gives it
+         "-c", str(path), "-o", "/dev/null",
+         "-Rpass-analysis=kernel-resource-usage"],
         capture_output=True, text=True, timeout=600)
     if r.returncode != 0:
         raise SystemExit(f"{path.name}: compile failed\n{r.stderr[-2000:]}")
