@@ -23,11 +23,12 @@ import dataclasses
 import itertools
 import time
 from dataclasses import dataclass, field
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Sequence
 
 import torch
 
 from ...ops import functional as OF
+from .lora import LoraBank
 from .model import (EXPERT_DTYPES, WEIGHT_DTYPES, LlamaConfig, LlamaModel,
                     MoEFFN, quantize_llama_, quantize_llama_expert_state,
                     quantize_llama_experts_, quantize_llama_state)
@@ -61,6 +62,9 @@ class Request:
     t_arrive: float = field(default_factory=time.monotonic)
     t_first_token: Optional[float] = None
     stream_cb: Optional[object] = None
+    adapter: Optional[str] = None  # LoRA adapter by name; None = the base
+    adapter_slot: int = -1         # its bank slot, -1 = none
+    adapter_key: Optional[tuple] = None  # (name, load count): its identity
 
     @property
     def custom_sampling(self) -> bool:
@@ -85,7 +89,9 @@ class LlamaEngine:
                  spec_attn: str = "rows",
                  moe_impl: Optional[str] = None,
                  weight_dtype: str = "bf16",
-                 expert_dtype: Optional[str] = None):
+                 expert_dtype: Optional[str] = None,
+                 lora_slots: int = 0, lora_rank: int = 16,
+                 lora_targets: Optional[Sequence[str]] = None):
         """tp: optional parallel.tp.TPGroup — head-sharded tensor parallelism
         (vllm_inference.py:180 --tensor-parallel-size role).  Every rank runs
         the same engine loop on identical requests; the KV cache holds only
@@ -166,6 +172,20 @@ class LlamaEngine:
         before the KV pool is sized; with init_weights=False the model is
         built with empty packed buffers.
 
+        lora_slots: adapter slots of multi-LoRA serving (docs/ENGINE.md), 1
+        to 32; 0 (default) allocates nothing and changes nothing.  With
+        slots, `load_adapter` puts a trained adapter into a bank of stacked
+        matrices (lora.LoraBank, allocated before the KV pool is sized),
+        `add_request(adapter=name)` selects it per request, and every lane
+        adds each row's own delta after the targeted projections with
+        ops.lora_apply_ (csrc/lora.hip); the per-slot adapter ids live on
+        the device beside pos_d, so graph decode serves a mixed batch in
+        one replay.  lora_rank is the bank's rank (16, 32 or 64; adapters
+        of a lower rank are zero-padded), lora_targets the projections
+        that take deltas: any of qkv, o_proj, gate_up, down — all four by
+        default, qkv and o_proj on an MoE config, where gate_up and down
+        raise ValueError.  tp with lora_slots > 0 raises ValueError.
+
         gpu_mem_util: fraction of free HBM the KV pool claims when
         kv_blocks is unset (--gpu-memory-utilization / --mem-fraction-static
         role, lfm_snapshot.py:316 / deepseek_v4_flash.py:255)."""
@@ -199,6 +219,10 @@ class LlamaEngine:
         self.cfg = dataclasses.replace(self.cfg, expert_dtype=expert_dtype)
         self.expert_dtype = expert_dtype
         self.tp = tp
+        if lora_slots and tp is not None and tp.world > 1:
+            raise ValueError("lora_slots > 0 under tensor parallelism is "
+                             "not supported")
+        self.lora_slots = lora_slots
         self.spec_tokens = spec_tokens
         self.spec_proposed = 0   # drafts offered
         self.spec_accepted = 0   # drafts accepted (emitted without a step)
@@ -272,6 +296,12 @@ class LlamaEngine:
                 torch.set_default_dtype(prev)
             self.model = self.model.to_empty(device=self.device)
         self.model.eval()
+        # adapter bank (outside the module tree) and who sits in which slot
+        self.lora = (LoraBank(self.cfg, lora_slots, lora_rank, lora_targets,
+                              device=self.device, dtype=dtype)
+                     if lora_slots else None)
+        self._adapters: Dict[str, tuple] = {}  # name -> (slot, load count)
+        self._adapter_loads = 0
         c = self.cfg
         if kv_blocks is None:
             if self.device.type == "cuda":
@@ -298,6 +328,8 @@ class LlamaEngine:
         self._step_count = 0
         self.preemptions = 0  # KV-pressure evictions (served, not errors)
         self._graph = None
+        self._graph_lora = None   # the decode graph with the adapter deltas
+        self.logits_lora_d = None
         self._slots: List[Optional[Request]] = [None] * max_batch
         # persistent device-side slot state (double as the graph's static bufs)
         dev = self.device
@@ -307,6 +339,9 @@ class LlamaEngine:
                                 dtype=torch.int32, device=dev)
         self.lens_d = torch.ones(max_batch, dtype=torch.int32, device=dev)
         self.active_d = torch.zeros(max_batch, dtype=torch.int32, device=dev)
+        # bank slot of each batch slot's adapter, -1 = none (read by decode)
+        self.adapter_d = (torch.full((max_batch,), -1, dtype=torch.int32,
+                                     device=dev) if lora_slots else None)
         self.temps_d = torch.zeros(max_batch, dtype=torch.float32, device=dev)
         # per-slot sampling parameters of requests that set any (written when
         # the slot is armed, reset when it is released): top_p 0 = "the
@@ -404,6 +439,58 @@ class LlamaEngine:
         eng.model.load_state_dict(sd, assign=True)
         return eng
 
+    # ------------------------------------------------ adapters
+
+    def _live_requests(self):
+        return itertools.chain(self.waiting, self.running, self.prefilling)
+
+    def load_adapter(self, name: str, state: Dict[str, torch.Tensor],
+                     alpha: float = 16.0) -> int:
+        """Make a trained adapter servable under `name`.  state holds
+        `blocks.<i>.<projection>.lora_a` [r, in] / `.lora_b` [out, r], the
+        names train.lora.lora_state_dict gives a wrapped LlamaModel, for any
+        subset of the engine's lora_targets; r may be below lora_rank.
+        alpha / r is folded into lora_b in fp32.  Returns the bank slot."""
+        if self.lora is None:
+            raise ValueError("the engine was built with lora_slots=0")
+        if not isinstance(name, str) or not name:
+            raise ValueError(f"adapter name must be a non-empty string, got "
+                             f"{name!r}")
+        if name in self._adapters:
+            raise ValueError(f"adapter {name!r} is already loaded")
+        used = {slot for slot, _ in self._adapters.values()}
+        free = [i for i in range(self.lora_slots) if i not in used]
+        if not free:
+            raise ValueError(f"all {self.lora_slots} adapter slots are in "
+                             f"use")
+        self.lora.write(free[0], state, alpha)
+        self._adapter_loads += 1
+        self._adapters[name] = (free[0], self._adapter_loads)
+        return free[0]
+
+    def unload_adapter(self, name: str) -> None:
+        """Free `name`'s slot.  Raises while a live request uses it."""
+        if name not in self._adapters:
+            raise ValueError(f"adapter {name!r} is not loaded")
+        if any(r.adapter == name for r in self._live_requests()):
+            raise ValueError(f"adapter {name!r} is in use by a live request")
+        slot, _ = self._adapters.pop(name)
+        self.lora.clear(slot)
+
+    @property
+    def adapters(self) -> List[str]:
+        return list(self._adapters)
+
+    def _lora_args(self, reqs, rows_per_req) -> dict:
+        """The model's adapter arguments for a forward whose rows belong to
+        `reqs`, rows_per_req[i] consecutive rows each; {} when none of them
+        has an adapter, so the forward is the base model's."""
+        if self.lora is None or all(r.adapter_slot < 0 for r in reqs):
+            return {}
+        ids = torch.tensor([r.adapter_slot for r in reqs], dtype=torch.int32)
+        idx = ids.repeat_interleave(torch.tensor(list(rows_per_req)))
+        return {"adapter_idx": idx.to(self.device), "lora_bank": self.lora}
+
     # ------------------------------------------------ request lifecycle
 
     def add_request(self, prompt: List[int], max_new_tokens: int = 64,
@@ -413,11 +500,16 @@ class LlamaEngine:
                     stop_seqs: Optional[List[List[int]]] = None,
                     logprobs: bool = False, top_k: int = 0,
                     top_p: Optional[float] = None, min_p: float = 0.0,
-                    seed: Optional[int] = None) -> int:
+                    seed: Optional[int] = None,
+                    adapter: Optional[str] = None) -> int:
         """top_k / top_p / min_p / seed are per-request sampling controls
         (docs/ENGINE.md): top_k 0 and min_p 0 are off, top_p None takes the
         engine-wide value, seed None the engine's per-step seed.  Out-of-
-        range values raise ValueError."""
+        range values raise ValueError.  adapter names a loaded LoRA adapter
+        (load_adapter); an unknown name raises ValueError."""
+        if adapter is not None and adapter not in self._adapters:
+            raise ValueError(f"unknown adapter {adapter!r} (loaded: "
+                             f"{sorted(self._adapters)})")
         if isinstance(top_k, bool) or not isinstance(top_k, int) or top_k < 0:
             raise ValueError(f"top_k must be an integer >= 0, got {top_k!r}")
         if top_p is not None and not 0.0 < float(top_p) <= 1.0:
@@ -440,6 +532,10 @@ class LlamaEngine:
                     want_logprobs=logprobs, top_k=top_k,
                     top_p=None if top_p is None else float(top_p),
                     min_p=float(min_p), seed=seed)
+        if adapter is not None:
+            r.adapter = adapter
+            r.adapter_slot = self._adapters[adapter][0]
+            r.adapter_key = (adapter, self._adapters[adapter][1])
         self._next_id += 1
         self.waiting.append(r)
         return r.req_id
@@ -453,8 +549,11 @@ class LlamaEngine:
 
     # ---- block-level prefix cache (refcounted, full prompt blocks only) ----
 
-    def _pc_chain_hashes(self, feed: List[int]) -> List[int]:
-        hs, h = [], 0
+    def _pc_chain_hashes(self, feed: List[int], key=None) -> List[int]:
+        """key: the identity of the request's adapter (name, load count), so
+        KV computed under one adapter is shared with no other and not with
+        the base; None (no adapter) starts the chain at 0."""
+        hs, h = [], 0 if key is None else hash(("lora",) + tuple(key))
         for b in range(len(feed) // BLOCK):
             h = hash((h, tuple(feed[b * BLOCK:(b + 1) * BLOCK])))
             hs.append(h)
@@ -485,7 +584,7 @@ class LlamaEngine:
         if not self.prefix_cache:
             return
         cached = self._feed(r)[: r.pos]
-        for i, h in enumerate(self._pc_chain_hashes(cached)):
+        for i, h in enumerate(self._pc_chain_hashes(cached, r.adapter_key)):
             bid = r.blocks[i]
             if bid in self._pc_hash or h in self._pc_map:
                 continue  # shared-in block, or same content cached elsewhere
@@ -516,6 +615,8 @@ class LlamaEngine:
             self.lens_d[i] = 1
             self.active_d[i] = 0
             self.bt_d[i].zero_()
+            if r.adapter_slot >= 0:
+                self.adapter_d[i] = -1
             if r.custom_sampling:
                 self.topk_d[i] = 0
                 self.topp_d[i] = 0.0
@@ -557,7 +658,8 @@ class LlamaEngine:
             self.cache_v[li][blks, :, offs] = vf.to(self.cache_v.dtype)
 
         last_pos = torch.tensor([x - 1 for x in lens], device=self.device)
-        logits = self.model.prefill(toks, kv_writer, last_pos=last_pos)
+        logits = self.model.prefill(toks, kv_writer, last_pos=last_pos,
+                                    **self._lora_args(group, [lmax] * n))
         temps = torch.tensor([r.temperature for r in group])
         first_d = self._sample_requests(logits, temps, group)
         lps = (self._logprobs_of(logits, first_d)
@@ -576,6 +678,8 @@ class LlamaEngine:
             bt = torch.tensor(r.blocks, device=self.device, dtype=torch.int32)
             self.bt_d[slot, : len(r.blocks)] = bt
             self.active_d[slot] = 1
+            if r.adapter_slot >= 0:
+                self.adapter_d[slot] = r.adapter_slot
             self.temps_d[slot] = r.temperature
             self._arm_sampling(r)
             self._pc_register(r)
@@ -595,7 +699,7 @@ class LlamaEngine:
         L = len(feed)
         shared: List[int] = []
         if self.prefix_cache:
-            hs = self._pc_chain_hashes(feed)
+            hs = self._pc_chain_hashes(feed, r.adapter_key)
             if hs and len(hs) * BLOCK == L:
                 hs = hs[:-1]  # always compute >= 1 token (the logits source)
             for h in hs:
@@ -754,9 +858,11 @@ class LlamaEngine:
 
     # ------------------------------------------------ decode
 
-    def _run_decode(self, limit: Optional[int] = None):
+    def _run_decode(self, limit: Optional[int] = None, lora: bool = False):
         """The captured computation: one token for every slot (graph mode
-        always runs the full width; eager mode slices to the live prefix)."""
+        always runs the full width; eager mode slices to the live prefix).
+        lora: add each slot's adapter delta, read from adapter_d on the
+        device."""
         lim = self.max_batch if limit is None else limit
         toks, pos = self.toks_d[:lim], self.pos_d[:lim]
         bt, lens = self.bt_d[:lim], self.lens_d[:lim]
@@ -772,6 +878,10 @@ class LlamaEngine:
             return OF.paged_decode(q, self.cache_k[li], self.cache_v[li],
                                    bt, lens, BLOCK)
 
+        if lora:
+            return self.model.decode_step(toks, pos, kv_append, kv_attend,
+                                          adapter_idx=self.adapter_d[:lim],
+                                          lora_bank=self.lora)
         return self.model.decode_step(toks, pos, kv_append, kv_attend)
 
     # ------------------------------------------------ chunked prefill
@@ -829,7 +939,8 @@ class LlamaEngine:
                 return OF.paged_decode(q, self.cache_k[li], self.cache_v[li],
                                        bt, lens, BLOCK)
 
-        logits = self.model.decode_step(toks, pos, kv_append, kv_attend)
+        logits = self.model.decode_step(toks, pos, kv_append, kv_attend,
+                                        **self._lora_args([r], [end - start]))
         r.pf_done = end
         r.pos = end
         if end < len(feed):
@@ -848,6 +959,8 @@ class LlamaEngine:
         self.bt_d[slot, : len(r.blocks)] = torch.tensor(
             r.blocks, device=dev, dtype=torch.int32)
         self.active_d[slot] = 1
+        if r.adapter_slot >= 0:
+            self.adapter_d[slot] = r.adapter_slot
         self.temps_d[slot] = r.temperature
         self._arm_sampling(r)
         self._pc_register(r)
@@ -944,7 +1057,10 @@ class LlamaEngine:
                 return OF.paged_decode(q, self.cache_k[li], self.cache_v[li],
                                        bt, lens, BLOCK)
 
-        logits = self.model.decode_step(toks, pos, kv_append, kv_attend)
+        logits = self.model.decode_step(
+            toks, pos, kv_append, kv_attend,
+            **self._lora_args([r for r, _, _ in plan],
+                              [len(drafts) + 1 for _, _, drafts in plan]))
         row_reqs = [None] * len(rows_tok)
         for r, base, drafts in plan:
             if r.presence_penalty or r.frequency_penalty:
@@ -979,39 +1095,47 @@ class LlamaEngine:
         A CUDAGraph destroyed during interpreter teardown (after the runtime)
         aborts the process with 'terminate called without an active
         exception' — call this from worker @exit hooks."""
-        self._graph = None
-        self.logits_d = None
+        self._graph = self._graph_lora = None
+        self.logits_d = self.logits_lora_d = None
         if self.device.type == "cuda":
             torch.cuda.synchronize()
 
-    def _ensure_graph(self):
-        if self._graph is not None:
+    def _ensure_graph(self, lora: bool = False):
+        """Two graphs at most: the base model's, which an engine with
+        adapter slots replays as long as no running request has an adapter
+        (so unused slots cost nothing), and the one with the deltas."""
+        if (self._graph_lora if lora else self._graph) is not None:
             return
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s), torch.no_grad():
             for _ in range(2):
-                self._run_decode()
+                self._run_decode(lora=lora)
         torch.cuda.current_stream().wait_stream(s)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g), torch.no_grad():
-            self.logits_d = self._run_decode()
-        self._graph = g
+            logits = self._run_decode(lora=lora)
+        if lora:
+            self._graph_lora, self.logits_lora_d = g, logits
+        else:
+            self._graph, self.logits_d = g, logits
 
     @torch.no_grad()
     def _decode_batch(self):
+        lora = any(r.adapter_slot >= 0 for r in self.running)
         if self.use_graph:
-            self._ensure_graph()
-            self._graph.replay()
-            logits = self.logits_d
+            self._ensure_graph(lora)
+            (self._graph_lora if lora else self._graph).replay()
+            logits = self.logits_lora_d if lora else self.logits_d
             lim = self.max_batch
         else:
             lim = max(r.slot for r in self.running) + 1
-            logits = self._run_decode(lim)
+            logits = self._run_decode(lim, lora)
         row_reqs = [self._slots[i] for i in range(lim)]
         if any(r is not None and (r.presence_penalty or r.frequency_penalty)
                for r in row_reqs):
-            logits = logits.clone() if logits is self.logits_d else logits
+            if logits is self.logits_d or logits is self.logits_lora_d:
+                logits = logits.clone()
             self._apply_penalties(logits, row_reqs)
         batched = any(r.custom_sampling for r in self.running)
         if batched:

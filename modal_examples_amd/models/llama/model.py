@@ -242,22 +242,35 @@ class LlamaBlock(nn.Module):
         self.hd = hd
         self.ffn_dim = cfg.ffn_dim // tp_world
 
-    def project_qkv(self, x):
+    def project_qkv(self, x, lora=None, li: int = 0):
         """x [B,S,d] → BSHD views of the fused projection (zero copies):
-        q [B,S,nq,hd], k/v [B,S,nkv,hd]."""
+        q [B,S,nq,hd], k/v [B,S,nkv,hd].  lora (lora.LoraRows) adds layer
+        li's adapter deltas to the projection output, as in out_proj / ffn."""
         B, S, _ = x.shape
         qkv = self.qkv(x)
+        if lora is not None:
+            lora.apply_(li, "qkv", qkv, x)
         q, k, v = qkv.split(
             [self.nq * self.hd, self.nkv * self.hd, self.nkv * self.hd], dim=-1
         )
         return (q.view(B, S, self.nq, self.hd), k.view(B, S, self.nkv, self.hd),
                 v.view(B, S, self.nkv, self.hd))
 
-    def ffn(self, x):
+    def out_proj(self, o, lora=None, li: int = 0):
+        y = self.o_proj(o)
+        if lora is not None:
+            lora.apply_(li, "o_proj", y, o)
+        return y
+
+    def ffn(self, x, lora=None, li: int = 0):
         if self.moe is not None:
             return self.moe(x)
         # fused kernel reads both halves of the gate_up output in place
-        return self.down(OF.glu_fused(self.gate_up(x), gelu=False))
+        if lora is None:
+            return self.down(OF.glu_fused(self.gate_up(x), gelu=False))
+        h = OF.glu_fused(lora.apply_(li, "gate_up", self.gate_up(x), x),
+                         gelu=False)
+        return lora.apply_(li, "down", self.down(h), h)
 
 
 class LlamaModel(nn.Module):
@@ -301,24 +314,44 @@ class LlamaModel(nn.Module):
         return self._rope_cache[key]
 
     @torch.no_grad()
-    def prefill(self, tokens: torch.Tensor, kv_writer=None, last_pos=None):
+    def _lora_rows(self, adapter_idx, lora_bank, rows: int):
+        if adapter_idx is None and lora_bank is None:
+            return None
+        if adapter_idx is None or lora_bank is None:
+            raise ValueError("adapter_idx and lora_bank go together")
+        if self.tp is not None:
+            raise ValueError("LoRA under tensor parallelism is not "
+                             "supported")
+        if adapter_idx.numel() != rows:
+            raise ValueError(f"adapter_idx has {adapter_idx.numel()} "
+                             f"entries for {rows} rows")
+        return lora_bank.bind(adapter_idx)
+
+    @torch.no_grad()
+    def prefill(self, tokens: torch.Tensor, kv_writer=None, last_pos=None,
+                adapter_idx=None, lora_bank=None):
         """tokens [B,S] → logits [B, vocab] (last position only).
         kv_writer(layer_idx, k, v): callback storing [B,nkv,S,hd] into cache.
         last_pos [B] int64: per-row index of the last REAL token — the ragged
         path right-pads shorter prompts and samples at each row's own end
-        (vLLM-style mixed-length prefill; role of vllm_inference.py:158-209)."""
+        (vLLM-style mixed-length prefill; role of vllm_inference.py:158-209).
+        adapter_idx int32 [B,S] with lora_bank (lora.LoraBank): each row's
+        adapter slot, -1 = none; the deltas are added after qkv, o_proj,
+        gate_up and down.  Without them the forward is the base model's."""
         x = self.embed(tokens)
+        lora = self._lora_rows(adapter_idx, lora_bank, tokens.numel())
         rc, rs = self._rope_tables(x.device)
         gpu = x.is_cuda
         for li, blk in enumerate(self.blocks):
             h = blk.attn_norm(x)
-            q, k, v = blk.project_qkv(h)  # BSHD views
+            q, k, v = blk.project_qkv(h, lora, li)  # BSHD views
             q = OF.rope(q.transpose(1, 2), rc, rs, inplace=gpu).transpose(1, 2)
             k = OF.rope(k.transpose(1, 2), rc, rs, inplace=gpu).transpose(1, 2)
             if kv_writer is not None:
                 kv_writer(li, k, v)  # [B,S,nkv_local,hd]
-            x = x + self._ar(blk.o_proj(OF.attention_qkv(q, k, v, causal=True)))
-            x = x + self._ar(blk.ffn(blk.ffn_norm(x)))
+            o = OF.attention_qkv(q, k, v, causal=True)
+            x = x + self._ar(blk.out_proj(o, lora, li))
+            x = x + self._ar(blk.ffn(blk.ffn_norm(x), lora, li))
         if last_pos is None:
             x = self.norm(x[:, -1:])
         else:
@@ -327,24 +360,29 @@ class LlamaModel(nn.Module):
         return self.lm_head(x)[:, 0].float()
 
     @torch.no_grad()
-    def decode_step(self, tokens, positions, kv_append, kv_attend):
+    def decode_step(self, tokens, positions, kv_append, kv_attend,
+                    adapter_idx=None, lora_bank=None):
         """One token per sequence. tokens [B], positions [B] int32;
         kv_append(li, k, v): store [B,nkv,1,hd] at per-seq positions;
-        kv_attend(li, q): paged attention of q [B,nq,hd] vs the cache."""
+        kv_attend(li, q): paged attention of q [B,nq,hd] vs the cache.
+        adapter_idx int32 [B] with lora_bank: as in prefill; the ids are
+        read on the device only, so the step still captures into a graph."""
         x = self.embed(tokens).unsqueeze(1)  # [B,1,d]
+        lora = self._lora_rows(adapter_idx, lora_bank, tokens.numel())
         rc, rs = self._rope_tables(x.device)
         gpu = x.is_cuda
         for li, blk in enumerate(self.blocks):
             h = blk.attn_norm(x)
-            q, k, v = blk.project_qkv(h)  # BSHD views [B,1,h,hd]
+            q, k, v = blk.project_qkv(h, lora, li)  # BSHD views [B,1,h,hd]
             q = OF.rope(q.transpose(1, 2), rc, rs, positions=positions,
                         inplace=gpu).transpose(1, 2)
             k = OF.rope(k.transpose(1, 2), rc, rs, positions=positions,
                         inplace=gpu).transpose(1, 2)
             kv_append(li, k, v)  # [B,1,nkv_local,hd]
             o = kv_attend(li, q[:, 0].contiguous() if not q[:, 0].is_contiguous() else q[:, 0])
-            x = x + self._ar(blk.o_proj(o.reshape(o.shape[0], 1, -1)))
-            x = x + self._ar(blk.ffn(blk.ffn_norm(x)))
+            x = x + self._ar(blk.out_proj(o.reshape(o.shape[0], 1, -1), lora,
+                                          li))
+            x = x + self._ar(blk.ffn(blk.ffn_norm(x), lora, li))
         x = self.norm(x[:, -1:])
         return self.lm_head(x)[:, 0].float()
 

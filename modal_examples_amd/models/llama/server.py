@@ -78,10 +78,12 @@ class LLMServer:
                frequency_penalty: float = 0.0, stop=None,
                logprobs: bool = False, top_p: Optional[float] = None,
                top_k: int = 0, min_p: float = 0.0,
-               seed: Optional[int] = None) -> int:
+               seed: Optional[int] = None,
+               adapter: Optional[str] = None) -> int:
         """Queue one request.  top_p / top_k / min_p / seed are the engine's
         per-request sampling controls; an out-of-range value raises
-        ValueError here, as a failed request does from wait()."""
+        ValueError here, as a failed request does from wait().  adapter
+        names a LoRA adapter loaded into the engine (ValueError if unknown)."""
         ids = self.tok.encode(prompt)
         seqs = [stop] if isinstance(stop, str) else list(stop or [])
         stop_ids = [self.tok.encode(q)[1:] for q in seqs]  # drop BOS
@@ -91,7 +93,8 @@ class LLMServer:
                 presence_penalty=presence_penalty,
                 frequency_penalty=frequency_penalty,
                 stop_seqs=[q for q in stop_ids if q], logprobs=logprobs,
-                top_k=top_k, top_p=top_p, min_p=min_p, seed=seed)
+                top_k=top_k, top_p=top_p, min_p=min_p, seed=seed,
+                adapter=adapter)
             self._events[rid] = threading.Event()
         self._wake.set()
         return rid
@@ -125,11 +128,13 @@ class LLMServer:
                  presence_penalty: float = 0.0,
                  frequency_penalty: float = 0.0,
                  top_p: Optional[float] = None, top_k: int = 0,
-                 min_p: float = 0.0, seed: Optional[int] = None) -> str:
+                 min_p: float = 0.0, seed: Optional[int] = None,
+                 adapter: Optional[str] = None) -> str:
         rid = self.submit(prompt, max_tokens, temperature,
                           presence_penalty=presence_penalty,
                           frequency_penalty=frequency_penalty, stop=stop,
-                          top_p=top_p, top_k=top_k, min_p=min_p, seed=seed)
+                          top_p=top_p, top_k=top_k, min_p=min_p, seed=seed,
+                          adapter=adapter)
         r = self.wait(rid)
         toks = list(r.out_tokens)
         # engine-side early stop leaves the matched stop tokens at the
@@ -172,6 +177,9 @@ def sampling_fields(body: dict, choice: int = 0) -> dict:
     if body.get("seed") is not None:
         out["seed"] = int(body["seed"]) + choice
     return out
+
+
+_sampling_fields = sampling_fields
 
 
 def create_openai_app(server: LLMServer):
@@ -227,8 +235,30 @@ def create_openai_app(server: LLMServer):
 
     @app.get("/v1/models")
     async def models():
+        """The base model, then every loaded LoRA adapter (a request selects
+        one by putting its name into `model`)."""
+        names = [server.model_name] + list(server.engine.adapters)
         return {"object": "list",
-                "data": [{"id": server.model_name, "object": "model"}]}
+                "data": [{"id": n, "object": "model"} for n in names]}
+
+    def model_error(body: dict):
+        """The 404 of a request whose `model` is neither the base model nor
+        a loaded adapter (OpenAI's error shape), else None."""
+        model = body.get("model")
+        if not model or model == server.model_name \
+                or model in server.engine.adapters:
+            return None
+        return JSONResponse(status_code=404, content={"error": {
+            "message": f"The model {model!r} does not exist",
+            "type": "invalid_request_error", "param": "model",
+            "code": "model_not_found"}})
+
+    def sampling_fields(body: dict, choice: int = 0) -> dict:
+        """The module-level fields plus the adapter `model` selects."""
+        out = _sampling_fields(body, choice)
+        if body.get("model") and body["model"] != server.model_name:
+            out["adapter"] = body["model"]
+        return out
 
     async def _run(prompt: str, max_tokens: int, temperature: float,
                    stream: bool, chat: bool, stop=None,
@@ -319,6 +349,9 @@ def create_openai_app(server: LLMServer):
 
     @app.post("/v1/completions")
     async def completions(body: dict):
+        err = model_error(body)
+        if err is not None:
+            return err
         n = int(body.get("n", 1) or 1)
         if n > 1 and not body.get("stream"):
             # OpenAI `n`: independent sampled completions (per-row gumbel
@@ -375,6 +408,9 @@ def create_openai_app(server: LLMServer):
 
     @app.post("/v1/chat/completions")
     async def chat_completions(body: dict):
+        err = model_error(body)
+        if err is not None:
+            return err
         msgs = body.get("messages", [])
         prompt = "\n".join(m.get("content", "") for m in msgs)
         return await _run(prompt, int(body.get("max_tokens", 64)),

@@ -32,6 +32,7 @@ HIP_SOURCES = [
     "conv3x3.hip",
     "moe.hip",
     "linear_w4.hip",
+    "lora.hip",
 ]
 
 # Per-source compiler flags beyond `common`; scripts/check_kernel_resources.py
@@ -42,6 +43,8 @@ HIP_SOURCES = [
 EXTRA_FLAGS = {
     "attention_decode_packed.hip": ["-Xclang", "-target-feature", "-Xclang",
                                     "-packed-fp32-ops"],
+    "lora.hip": ["-Xclang", "-target-feature", "-Xclang",
+                 "-packed-fp32-ops"],
 }
 
 

@@ -103,6 +103,15 @@ int moe_ffn_w4_bf16(const void*, const void*, const void*, const void*,
 int linear_w4_plan(long long, int, int, int);
 int linear_w4_bf16(const void*, const void*, const void*, float*, void*,
                    long long, int, int, int, hipStream_t);
+// the LoRA launchers return 0 once launched, non-zero (nothing launched)
+// for a shape they do not support; lora_plan: the K-slice count of the
+// shrink GEMM (= planes of the workspace), 0 for an unsupported K
+int lora_max_tiles(long long, int);
+int lora_plan(int, int);
+int lora_align_i32(const int*, int*, long long, int, hipStream_t);
+int lora_apply_bf16(void*, const void*, const void*, const void*, const int*,
+                    float*, long long, int, int, int, int, int, int,
+                    hipStream_t);
 }
 
 namespace {
@@ -1071,6 +1080,100 @@ int64_t linear_w4_splits(int64_t M, int64_t N, int64_t K, int64_t splits) {
   return linear_w4_plan(M, (int)N, (int)K, (int)splits);
 }
 
+// ---------------------------------------------------------------- multi-LoRA
+// Supported: S <= 32 adapters, R in {16, 32, 64}, K a multiple of 64, O a
+// multiple of 128, any N.  Every check raises before anything is launched;
+// every workspace size depends on shapes only, so both entries capture into
+// a graph.
+
+// idx int32 [N] -> the schedule int32 [tiles*33 + 1] (slot_map, tile_adapter,
+// num_tiles; tiles = N/32 + slots).  Ids outside [0, slots) take no slot.
+torch::Tensor lora_schedule(torch::Tensor idx, int64_t slots) {
+  TORCH_CHECK(idx.is_cuda() && idx.scalar_type() == torch::kInt32 &&
+                  idx.dim() == 1 && idx.is_contiguous(),
+              "lora_schedule: idx must be int32 [N] contiguous on GPU");
+  TORCH_CHECK(slots >= 1 && slots <= 32, "lora_schedule: slots=", slots,
+              " (supported: 1..32)");
+  const int64_t N = idx.size(0);
+  TORCH_CHECK(N < (1ll << 30), "lora_schedule: idx has too many rows");
+  const int64_t tiles = lora_max_tiles(N, (int)slots);
+  auto sched = torch::empty({tiles * 33 + 1}, idx.options());
+  if (N == 0) return sched;
+  int rc = lora_align_i32(idx.data_ptr<int>(), sched.data_ptr<int>(), N,
+                          (int)slots, cur_stream());
+  TORCH_CHECK(rc == 0, "lora_schedule: shape not supported by the kernel (N=",
+              N, " slots=", slots, ")");
+  return sched;
+}
+
+// y bf16 [N,O] += (x [N,K] . A[s]^T) . B[s]^T per row, in place, s the row's
+// adapter in the schedule; bank_a [S,R,K], bank_b [S,O,R] bf16.  slices = 0
+// takes the kernel's K-slice rule and swap = 1 its expand layout; other
+// values are for tests and benchmarks only — the public op never passes them.
+void lora_apply_(torch::Tensor y, torch::Tensor x, torch::Tensor bank_a,
+                 torch::Tensor bank_b, torch::Tensor sched, int64_t slices,
+                 bool swap) {
+  check_bf16(y, "y");
+  check_bf16(x, "x");
+  check_bf16(bank_a, "bank_a");
+  check_bf16(bank_b, "bank_b");
+  TORCH_CHECK(y.dim() == 2 && x.dim() == 2 && bank_a.dim() == 3 &&
+                  bank_b.dim() == 3,
+              "lora_apply_: y must be [N,O], x [N,K], bank_a [S,R,K], bank_b "
+              "[S,O,R]");
+  const int64_t N = x.size(0), K = x.size(1), O = y.size(1),
+                S = bank_a.size(0), R = bank_a.size(1);
+  TORCH_CHECK(y.size(0) == N, "lora_apply_: y has ", y.size(0), " rows, x ",
+              N);
+  TORCH_CHECK(S >= 1 && S <= 32, "lora_apply_: bank_a has S=", S,
+              " adapters (supported: 1..32)");
+  TORCH_CHECK(R == 16 || R == 32 || R == 64, "lora_apply_: bank_a has rank ",
+              R, " (supported: 16, 32, 64)");
+  TORCH_CHECK(K >= 64 && K % 64 == 0, "lora_apply_: x has K=", K,
+              " (must be a multiple of 64)");
+  TORCH_CHECK(O >= 128 && O % 128 == 0, "lora_apply_: y has O=", O,
+              " (must be a multiple of 128)");
+  TORCH_CHECK(bank_a.size(2) == K && bank_b.size(0) == S &&
+                  bank_b.size(1) == O && bank_b.size(2) == R,
+              "lora_apply_: bank_a ", bank_a.sizes(), " / bank_b ",
+              bank_b.sizes(), " do not match [S,R,K] / [S,O,R] with K=", K,
+              " O=", O);
+  TORCH_CHECK(N < (1ll << 30) && K < (1ll << 31) && O < (1ll << 31) &&
+                  slices >= 0 && slices < (1ll << 31),
+              "lora_apply_: size out of range");
+  const int64_t tiles = lora_max_tiles(N, (int)S);
+  TORCH_CHECK(sched.is_cuda() && sched.scalar_type() == torch::kInt32 &&
+                  sched.dim() == 1 && sched.is_contiguous() &&
+                  sched.size(0) == tiles * 33 + 1,
+              "lora_apply_: sched is not a lora_schedule of N=", N,
+              " rows over ", S, " slots");
+  for (const torch::Tensor* t : {&x, &bank_a, &bank_b, &sched})
+    TORCH_CHECK(t->device() == y.device(),
+                "lora_apply_: all tensors must be on y's device");
+  // the kernels read 16 B fragments and update y in 8 B runs
+  for (const torch::Tensor* t : {&y, &x, &bank_a, &bank_b})
+    TORCH_CHECK((uintptr_t)t->data_ptr() % 16 == 0,
+                "lora_apply_: operands must be 16-byte aligned");
+  const int Z = lora_plan((int)K, (int)slices);
+  TORCH_CHECK(Z >= 1, "lora_apply_: K=", K, " with slices=", slices,
+              " not supported by the kernel");
+  if (N == 0) return;
+  auto ws = torch::empty({Z, tiles * 32, R},
+                         x.options().dtype(torch::kFloat32));
+  int rc = lora_apply_bf16(y.data_ptr(), x.data_ptr(), bank_a.data_ptr(),
+                           bank_b.data_ptr(), sched.data_ptr<int>(),
+                           ws.data_ptr<float>(), N, (int)K, (int)O, (int)S,
+                           (int)R, (int)slices, swap ? 1 : 0, cur_stream());
+  TORCH_CHECK(rc == 0, "lora_apply_: shape not supported by the kernel (N=",
+              N, " K=", K, " O=", O, " S=", S, " R=", R, ")");
+}
+
+int64_t lora_slices(int64_t K, int64_t slices) {
+  TORCH_CHECK(K < (1ll << 31) && slices >= 0 && slices < (1ll << 31),
+              "lora_slices: size out of range");
+  return lora_plan((int)K, (int)slices);
+}
+
 torch::Tensor sample_gumbel(torch::Tensor logits, double temperature,
                             int64_t seed) {
   TORCH_CHECK(logits.is_cuda() && logits.scalar_type() == torch::kFloat32,
@@ -1316,6 +1419,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "K slices linear_w4 uses for (M, N, K); 0 = unsupported shape",
         pybind11::arg("M"), pybind11::arg("N"), pybind11::arg("K"),
         pybind11::arg("splits") = 0);
+  m.def("lora_schedule", &lora_schedule,
+        "multi-LoRA row schedule: rows grouped by adapter into 32-row tiles",
+        py::arg("idx"), py::arg("slots"));
+  m.def("lora_apply_", &lora_apply_,
+        "multi-LoRA delta in place: grouped shrink/expand MFMA GEMMs",
+        py::arg("y"), py::arg("x"), py::arg("bank_a"), py::arg("bank_b"),
+        py::arg("sched"), py::arg("slices") = 0, py::arg("swap") = true);
+  m.def("lora_slices", &lora_slices,
+        "K slices lora_apply_ uses for inner width K; 0 = unsupported",
+        py::arg("K"), py::arg("slices") = 0);
   m.def("scale_in_dev", &scale_in_dev, "x * 1/sqrt(sigma^2+1), device sigma");
   m.def("cfg_euler_dev", &cfg_euler_dev, "graph-capturable CFG+Euler step");
   m.def("step_advance", &step_advance, "increment device step counter");

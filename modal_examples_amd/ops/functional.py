@@ -10,7 +10,7 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -792,6 +792,98 @@ def moe_ffn_w4(x, gate_up_q, gate_up_s, down_q, down_s, weights, idx):
                                   weights, idx)
     return ext.moe_ffn_w4(x, gate_up_q, gate_up_s, down_q, down_s,
                           weights.float().contiguous(), idx.contiguous())
+
+
+# ---- multi-LoRA delta.  Supported shapes (csrc/lora.hip): S <= 32 adapter
+# slots, bank rank R in {16, 32, 64}, K a multiple of 64, O a multiple of 128,
+# any N, contiguous operands.  As above, the checks run on every device
+# before the dispatch.
+
+class LoraSchedule(NamedTuple):
+    """What lora_schedule returns: the per-row adapter ids it was built from,
+    the slot count, and on the GPU the device-side schedule (rows grouped by
+    adapter into 32-row tiles; csrc/lora.hip).  Valid until idx changes."""
+    idx: torch.Tensor
+    slots: int
+    sched: Optional[torch.Tensor]
+
+
+def lora_schedule(idx, slots: int) -> LoraSchedule:
+    """The row schedule of a batch for lora_apply_: idx int32 [N] holds each
+    row's adapter slot, anything outside [0, slots) meaning "no adapter".
+    One schedule serves every projection of every layer of a forward.  One
+    kernel, nothing read back to the host."""
+    if idx.dtype is not torch.int32:
+        raise TypeError(f"idx must be int32, got {idx.dtype}")
+    if idx.dim() != 1 or not idx.is_contiguous():
+        raise ValueError(f"idx must be a contiguous [N] vector, got "
+                         f"{tuple(idx.shape)}")
+    if isinstance(slots, bool) or not isinstance(slots, int) \
+            or not 1 <= slots <= 32:
+        raise ValueError(f"slots={slots!r} (supported: 1..32)")
+    ext = _ext_for(idx, any_dtype=True)
+    return LoraSchedule(idx, slots,
+                        None if ext is None else ext.lora_schedule(idx, slots))
+
+
+def _check_lora(y, x, bank_a, bank_b, sched):
+    if x.dim() != 2 or y.dim() != 2 or y.shape[0] != x.shape[0]:
+        raise ValueError(f"y must be [N, O] and x [N, K], got "
+                         f"{tuple(y.shape)}, {tuple(x.shape)}")
+    N, K = x.shape
+    O = y.shape[1]
+    if bank_a.dim() != 3 or bank_a.shape[2] != K:
+        raise ValueError(f"bank_a must be [S, R, K={K}], got "
+                         f"{tuple(bank_a.shape)}")
+    S, R = bank_a.shape[:2]
+    if not 1 <= S <= 32:
+        raise ValueError(f"bank_a has S={S} adapters (supported: 1..32)")
+    if R not in (16, 32, 64):
+        raise ValueError(f"bank_a has rank {R} (supported: 16, 32, 64)")
+    if tuple(bank_b.shape) != (S, O, R):
+        raise ValueError(f"bank_b must be [S={S}, O={O}, R={R}], got "
+                         f"{tuple(bank_b.shape)}")
+    if K % 64 != 0 or K < 64:
+        raise ValueError(f"x has K={K} (must be a multiple of 64)")
+    if O % 128 != 0 or O < 128:
+        raise ValueError(f"y has O={O} (must be a multiple of 128)")
+    if not isinstance(sched, LoraSchedule):
+        raise TypeError("sched must come from lora_schedule")
+    if sched.slots != S or sched.idx.shape[0] != N:
+        raise ValueError(f"sched was built for {sched.idx.shape[0]} rows "
+                         f"over {sched.slots} slots, the call has N={N}, "
+                         f"S={S}")
+    for name, t in (("y", y), ("x", x), ("bank_a", bank_a),
+                    ("bank_b", bank_b)):
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+        if t.dtype is not y.dtype or t.device != y.device:
+            raise ValueError(f"{name} must have y's dtype and device "
+                             f"({y.dtype}, {y.device}), got {t.dtype}, "
+                             f"{t.device}")
+    if sched.idx.device != y.device:
+        raise ValueError("sched must live on y's device")
+
+
+def lora_apply_(y, x, bank_a, bank_b, sched):
+    """The multi-adapter LoRA delta of one projection, in place
+    (csrc/lora.hip): y[n] += (x[n] . bank_a[s]^T) . bank_b[s]^T with s the
+    row's adapter in `sched`; rows without an adapter are not touched.
+
+    y [N, O] and x [N, K]; bank_a [S, R, K]; bank_b [S, O, R] with alpha / r
+    folded in; sched from lora_schedule over the same N and S.  On the GPU
+    nothing depends on the adapter ids but the data, so the call captures
+    into a graph; a row's result is bitwise reproducible and independent of
+    the batch around it.  Returns y."""
+    _check_lora(y, x, bank_a, bank_b, sched)
+    if y.shape[0] == 0:
+        return y
+    ext = _ext_for(y, x, bank_a, bank_b)
+    if ext is None:
+        y.copy_(ref.lora_apply_ref(y, x, bank_a, bank_b, sched.idx))
+        return y
+    ext.lora_apply_(y, x, bank_a, bank_b, sched.sched)
+    return y
 
 
 # ---- int4 weight-only linear.  Supported shapes (csrc/linear_w4.hip): K a

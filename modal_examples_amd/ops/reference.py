@@ -604,3 +604,69 @@ def linear_w4_bound_ref(x, qweight, scales, bf16_points=False):
     if bf16_points:
         want = want.to(torch.bfloat16).double()
     return want, tol
+
+
+# ---- multi-LoRA delta (csrc/lora.hip).  bank_a [S, R, K], bank_b [S, O, R]
+# with alpha / r folded into bank_b; idx [N] picks a row's adapter, an id
+# outside [0, S) means "no adapter".
+
+def lora_apply_ref(y, x, bank_a, bank_b, idx):
+    """y [N, O] with, for every row n whose s = idx[n] lies in [0, S),
+    y[n] + (x[n] . bank_a[s]^T) . bank_b[s]^T: a per-row gather of the two
+    adapter matrices, the products and the sum in fp64, one rounding to y's
+    dtype.  The other rows are returned as they are."""
+    S = bank_a.shape[0]
+    ii = idx.long()
+    on = (ii >= 0) & (ii < S)
+    out = y.clone()
+    if on.any():
+        sel = ii[on]
+        t = torch.einsum("nk,nrk->nr", x[on].double(), bank_a[sel].double())
+        d = torch.einsum("nr,nor->no", t, bank_b[sel].double())
+        out[on] = (y[on].double() + d).to(y.dtype)
+    return out
+
+
+def lora_bound_ref(y, x, bank_a, bank_b, idx):
+    """(want, tol) in fp64, per element, for a bf16 implementation of
+    lora_apply_ref that accumulates in fp32, keeps t = x . A^T unrounded by
+    feeding it to the second product as hi = bf16(t) plus lo = bf16(t - hi),
+    and rounds to bf16 once, at the output.
+
+      want   float(y) + t . B^T in fp64 (y itself on rows without adapter)
+      D      sum_r (sum_k |x||A|) |B|: the absolute-value products through
+             both GEMMs
+      E      ((K + 2R) * 2^-23 + 2^-16) * D + 2^-23 * |want|
+      tol    2^-8 * (|want| + E) + E          (0 on rows without adapter)
+
+    The three terms.  (1) Rounding the fp32 result v to bf16 (8 significant
+    bits) moves it by at most 2^-8 |v|, and |v| <= |want| + E.  (2) The fp32
+    accumulation: t sums K exact bf16 products and the second GEMM 2R of
+    them (hi and lo), in any order and across the K-slice partials, each
+    addition off by at most one unit in the last place, 2^-23 of the partial
+    sum, whose magnitude the absolute-value products bound; that covers a
+    matrix unit that truncates as well as one that rounds to nearest.  The
+    final fp32 addition to y gives the 2^-23 |want|.  (3) hi + lo misses t by
+    at most 2^-8 * 2^-8 = 2^-16 of |t|, two bf16 roundings deep, which
+    reaches the output through |B|, so again as a share of D.  Nothing is
+    added on top."""
+    S, R, K = bank_a.shape
+    ii = idx.long().cpu()
+    on = (ii >= 0) & (ii < S)
+    want = y.detach().double().cpu()
+    tol = torch.zeros_like(want)
+    if on.any():
+        sel = ii[on]
+        xa = x.detach().cpu()[on].double()
+        a = bank_a.detach().cpu()[sel].double()
+        b = bank_b.detach().cpu()[sel].double()
+        t = torch.einsum("nk,nrk->nr", xa, a)
+        w = want[on] + torch.einsum("nr,nor->no", t, b)
+        D = torch.einsum("nr,nor->no",
+                         torch.einsum("nk,nrk->nr", xa.abs(), a.abs()),
+                         b.abs())
+        E = ((K + 2 * R) * 2.0 ** -23 + 2.0 ** -16) * D \
+            + 2.0 ** -23 * w.abs()
+        want[on] = w
+        tol[on] = 2.0 ** -8 * (w.abs() + E) + E
+    return want, tol
