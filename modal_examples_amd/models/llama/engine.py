@@ -31,7 +31,8 @@ from ...ops import functional as OF
 from .lora import LoraBank
 from .model import (EXPERT_DTYPES, WEIGHT_DTYPES, LlamaConfig, LlamaModel,
                     MoEFFN, quantize_llama_, quantize_llama_expert_state,
-                    quantize_llama_experts_, quantize_llama_state)
+                    quantize_llama_experts_, quantize_llama_fp8_,
+                    quantize_llama_fp8_state, quantize_llama_state)
 
 BLOCK = 16
 
@@ -144,8 +145,8 @@ class LlamaEngine:
         decodes eagerly whatever use_graph says; "fused" captures and
         replays like a dense model.  Every other lane calls the same FFN.
 
-        weight_dtype: "bf16" (default) or "int4".  "int4" holds qkv, o_proj,
-        gate_up and down of every block as 4-bit weights with one bf16 scale
+        weight_dtype: "bf16" (default), "int4" or "fp8".  "int4" holds qkv,
+        o_proj, gate_up and down of every block as 4-bit weights with one bf16 scale
         per 128 inputs (ops.quantize_w4; model.QuantLinear): 0.52 bytes per
         weight instead of 2.  Decode batches run them on the
         csrc/linear_w4.hip kernel, inside the decode graph like the bf16
@@ -157,7 +158,15 @@ class LlamaEngine:
         empty packed buffers for load_state_dict(assign=True).  Under tp the
         shards are quantized, and a shard whose input width is no multiple
         of 128 raises.  MoE configs raise ValueError: their experts have a
-        knob of their own, expert_dtype.
+        knob of their own, expert_dtype.  "fp8" holds the same four
+        projections as e4m3 bytes with one fp32 scale per output channel
+        (ops.quantize_fp8; model.Fp8Linear), 1 byte per weight, and
+        quantizes the activations per token at run time: batches up to
+        Fp8Linear.M_KERNEL rows run on the csrc/linear_fp8.hip kernels
+        inside the decode graph, larger ones dequantize into a scratch
+        weight.  Everything else said for "int4" (what stays in `dtype`,
+        quantization before the KV pool is sized, init_weights=False, tp,
+        MoE configs) holds for it unchanged.
 
         expert_dtype: "bf16" or "int4"; None keeps cfg.expert_dtype.  "int4"
         holds the experts of every MoE block as 4-bit weights with one bf16
@@ -198,10 +207,10 @@ class LlamaEngine:
         if weight_dtype not in WEIGHT_DTYPES:
             raise ValueError(f"weight_dtype must be one of {WEIGHT_DTYPES}, "
                              f"got {weight_dtype!r}")
-        if weight_dtype == "int4" and self.cfg.n_experts > 0:
-            raise ValueError("weight_dtype='int4' does not cover MoE "
-                             "experts; use weight_dtype='bf16' for an MoE "
-                             "config")
+        if weight_dtype != "bf16" and self.cfg.n_experts > 0:
+            raise ValueError(f"weight_dtype={weight_dtype!r} does not cover "
+                             f"MoE experts; use weight_dtype='bf16' for an "
+                             f"MoE config")
         self.weight_dtype = weight_dtype
         if expert_dtype is None:
             expert_dtype = self.cfg.expert_dtype
@@ -273,9 +282,11 @@ class LlamaEngine:
                 self.model = LlamaModel(
                     dataclasses.replace(self.cfg, expert_dtype="bf16"),
                     tp=tp).to(self.device, dtype)
-            if weight_dtype == "int4" or expert_dtype == "int4":
+            if weight_dtype != "bf16" or expert_dtype == "int4":
                 if weight_dtype == "int4":
                     quantize_llama_(self.model)
+                elif weight_dtype == "fp8":
+                    quantize_llama_fp8_(self.model)
                 else:
                     quantize_llama_experts_(self.model)
                 if self.device.type == "cuda":
@@ -364,7 +375,8 @@ class LlamaEngine:
         reference role: sglang_snapshot.py:176-218 warm/sleep/wake).  An
         int4 engine writes its packed `qweight` / `scales` tensors, an
         int4-expert engine its `gate_up_q` / `gate_up_s` / `down_q` /
-        `down_s` buffers."""
+        `down_s` buffers, an fp8 engine its `qweight` / `wscale` tensors
+        (which `from_safetensors` does not read back yet)."""
         from ...gpu import fastload
 
         return fastload.save_file(dict(self.model.state_dict()), path)
@@ -383,7 +395,9 @@ class LlamaEngine:
         holds; asking for "bf16" raises, and so does tp.world > 1, whose
         shards would cut through packed words).  A bf16 file with
         weight_dtype="int4" is sharded first, if tp is set, and then
-        quantized on the device.  The same holds for expert_dtype: a file
+        quantized on the device, and so it is with weight_dtype="fp8" (files
+        that already hold fp8 weights are refused).  The same holds for
+        expert_dtype: a file
         with `.gate_up_q` keys defaults it to "int4" and refuses "bf16", and
         a bf16 file with expert_dtype="int4" is quantized on the device after
         loading."""
@@ -392,6 +406,10 @@ class LlamaEngine:
         from ...gpu import fastload
 
         header, _, _ = fastload._parse(path)
+        if any(k.endswith(".wscale") for k in header):
+            raise ValueError(f"{path} holds fp8 weights; loading them is not "
+                             f"supported: boot the bf16 checkpoint with "
+                             f"weight_dtype='fp8' instead")
         packed = any(k.endswith(".qweight") for k in header)
         kw.setdefault("weight_dtype", "int4" if packed else "bf16")
         if packed and kw["weight_dtype"] != "int4":
@@ -434,6 +452,8 @@ class LlamaEngine:
             sd = {k: v.contiguous() for k, v in sd.items()}
         if eng.weight_dtype == "int4" and not packed:
             sd = quantize_llama_state(sd)
+        if eng.weight_dtype == "fp8":
+            sd = quantize_llama_fp8_state(sd)
         if eng.expert_dtype == "int4" and not packed_experts:
             sd = quantize_llama_expert_state(sd)
         eng.model.load_state_dict(sd, assign=True)

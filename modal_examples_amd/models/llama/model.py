@@ -8,7 +8,8 @@ MI355X mapping:
   K7 prefill  → gfx950 flash attention (causal, GQA, D=128)
   K6 decode   → gfx950 paged decode kernel over the paged KV cache
   RMSNorm / RoPE / SwiGLU → fused gfx950 kernels
-  QKV and gate_up projections → single fused GEMMs (hipBLASLt)
+  QKV and gate_up projections → single fused GEMMs (hipBLASLt), or the
+  int4 / fp8 kernels under weight_dtype (QuantLinear, Fp8Linear)
 """
 from __future__ import annotations
 
@@ -56,7 +57,7 @@ class LlamaConfig:
                            rope_base=10000.0, max_seq=512, n_experts=4)
 
 
-WEIGHT_DTYPES = ("bf16", "int4")
+WEIGHT_DTYPES = ("bf16", "int4", "fp8")
 EXPERT_DTYPES = ("bf16", "int4")
 
 
@@ -128,6 +129,82 @@ class QuantLinear(nn.Module):
                 f"out_features={self.out_features}, int4 g128")
 
 
+class Fp8Linear(nn.Module):
+    """Bias-free linear layer over fp8 weights (ops.quantize_fp8): buffers
+    `qweight` float8_e4m3fn [out, in] and `wscale` fp32 [out], activations
+    quantized per row at run time ("W8A8 dynamic").
+
+    Two lanes, as QuantLinear.  Up to M_KERNEL rows the forward is
+    ops.linear_fp8: on the GPU the row-quantization kernel and the fp8 MFMA
+    GEMM of csrc/linear_fp8.hip, which multiply the fp8 values exactly and
+    apply both scales to the fp32 sum.  Above that the weight is dequantized
+    into a scratch tensor of the activation dtype and goes through the
+    ordinary GEMM on the unquantized activations; in bf16 that rounds every
+    w_hat = wscale * q to bf16 and skips the activation quantization, so the
+    two lanes differ by those roundings.  On the CPU, in fp32 or under
+    autograd, the kernel lane is the reference composition."""
+
+    # rows up to which the kernel lane is taken.  Measured
+    # (profiles/linear_fp8.txt, second table, "fp8" against "fp8deq"): at
+    # 1024 rows the kernel lane beats the dequantize lane on three of the
+    # four Llama-3-8B projections and is level on the fourth (142 / 147,
+    # 107 / 106, 510 / 749, 269 / 427 us), at 2048 rows it loses on all four
+    # (273 / 179, 204 / 127, 962 / 898, 508 / 491 us).  1024 is the largest
+    # measured count on the kernel's side of the crossover.
+    M_KERNEL = 1024
+
+    def __init__(self, in_features: int, out_features: int, device=None):
+        super().__init__()
+        if in_features % 128 != 0 or in_features < 128:
+            raise ValueError(f"Fp8Linear: in_features={in_features} must "
+                             f"be a multiple of 128")
+        if out_features % 64 != 0 or out_features < 64:
+            raise ValueError(f"Fp8Linear: out_features={out_features} "
+                             f"must be a multiple of 64")
+        self.in_features, self.out_features = in_features, out_features
+        self.register_buffer("qweight", torch.zeros(
+            out_features, in_features, dtype=torch.float8_e4m3fn,
+            device=device))
+        self.register_buffer("wscale", torch.ones(
+            out_features, dtype=torch.float32, device=device))
+
+    @classmethod
+    def from_linear(cls, lin: nn.Linear) -> "Fp8Linear":
+        if lin.bias is not None:
+            raise ValueError("Fp8Linear has no bias")
+        w = lin.weight.detach()
+        if w.dtype not in (torch.bfloat16, torch.float32):
+            w = w.float()
+        m = cls(lin.in_features, lin.out_features, device="meta")
+        m.qweight, m.wscale = OF.quantize_fp8(w.contiguous())
+        return m
+
+    def _apply(self, fn, recurse=True):
+        # module.to(dtype) casts every floating buffer; both are what they
+        # are by format.  The weight bytes are kept aside (a cast to bf16
+        # and back would be exact but doubles the memory in between); the
+        # scale's round trip would not be exact, so it is moved by device
+        # only.
+        q, s = self.qweight, self.wscale
+        super()._apply(fn, recurse)
+        if self.qweight.dtype is not torch.float8_e4m3fn:
+            self.qweight = q.to(self.qweight.device)
+        if self.wscale.dtype is not torch.float32:
+            self.wscale = s.to(self.wscale.device)
+        return self
+
+    def forward(self, x):
+        rows = x.numel() // self.in_features
+        if rows <= self.M_KERNEL:
+            return OF.linear_fp8(x, self.qweight, self.wscale)
+        w = OF.dequantize_fp8(self.qweight, self.wscale).to(x.dtype)
+        return nn.functional.linear(x, w)
+
+    def extra_repr(self):
+        return (f"in_features={self.in_features}, "
+                f"out_features={self.out_features}, fp8 e4m3 per-channel")
+
+
 QUANT_PROJECTIONS = ("qkv", "o_proj", "gate_up", "down")
 
 
@@ -160,6 +237,38 @@ def quantize_llama_state(state: dict) -> dict:
             q, s = OF.quantize_w4(v.contiguous())
             out[k[:-len("weight")] + "qweight"] = q
             out[k[:-len("weight")] + "scales"] = s
+        else:
+            out[k] = v
+    return out
+
+
+def quantize_llama_fp8_(model: "LlamaModel") -> "LlamaModel":
+    """`quantize_llama_` for fp8: the four block projections become
+    Fp8Linear modules, one projection at a time."""
+    for blk in model.blocks:
+        if blk.moe is not None:
+            raise ValueError("fp8 weights do not cover MoE experts")
+        for name in QUANT_PROJECTIONS:
+            lin = getattr(blk, name)
+            if isinstance(lin, nn.Linear):
+                setattr(blk, name, Fp8Linear.from_linear(lin))
+    model.weight_dtype = "fp8"
+    return model
+
+
+def quantize_llama_fp8_state(state: dict) -> dict:
+    """`quantize_llama_state` for fp8: the four block projections replaced
+    by their `qweight` / `wscale` pair."""
+    out = {}
+    for k, v in state.items():
+        parts = k.split(".")
+        if (len(parts) == 4 and parts[0] == "blocks"
+                and parts[2] in QUANT_PROJECTIONS and parts[3] == "weight"):
+            if v.dtype not in (torch.bfloat16, torch.float32):
+                v = v.float()
+            q, s = OF.quantize_fp8(v.contiguous())
+            out[k[:-len("weight")] + "qweight"] = q
+            out[k[:-len("weight")] + "wscale"] = s
         else:
             out[k] = v
     return out
@@ -214,15 +323,16 @@ class LlamaBlock(nn.Module):
         if weight_dtype not in WEIGHT_DTYPES:
             raise ValueError(f"weight_dtype must be one of {WEIGHT_DTYPES}, "
                              f"got {weight_dtype!r}")
-        if weight_dtype == "int4":
+        if weight_dtype in ("int4", "fp8"):
             # built with buffers of the right shape (meta-device boot);
             # a shard whose K is no multiple of 128 raises here
             if cfg.n_experts > 0:
-                raise ValueError("weight_dtype='int4' does not cover MoE "
-                                 "experts")
+                raise ValueError(f"weight_dtype={weight_dtype!r} does not "
+                                 f"cover MoE experts")
+            quant = QuantLinear if weight_dtype == "int4" else Fp8Linear
 
             def linear(i, o, bias=False):
-                return QuantLinear(i, o)
+                return quant(i, o)
         else:
             linear = nn.Linear
         self.attn_norm = RMSNormK(d, cfg.norm_eps)
@@ -283,7 +393,8 @@ class LlamaModel(nn.Module):
         weight_dtype="int4" builds qkv, o_proj, gate_up and down of every
         block as QuantLinear modules with empty buffers (for loading a
         quantized state); `quantize_llama_` converts an initialised bf16
-        model in place."""
+        model in place.  weight_dtype="fp8" does the same with Fp8Linear
+        modules and `quantize_llama_fp8_`."""
         super().__init__()
         self.cfg = cfg
         self.weight_dtype = weight_dtype

@@ -33,6 +33,7 @@ HIP_SOURCES = [
     "moe.hip",
     "linear_w4.hip",
     "lora.hip",
+    "linear_fp8.hip",
 ]
 
 # Per-source compiler flags beyond `common`; scripts/check_kernel_resources.py
@@ -45,6 +46,10 @@ EXTRA_FLAGS = {
                                     "-packed-fp32-ops"],
     "lora.hip": ["-Xclang", "-target-feature", "-Xclang",
                  "-packed-fp32-ops"],
+    # no fast-math flag may join these: fp8_quant_rows_kernel's fp32
+    # divisions must stay correctly rounded (csrc/linear_fp8.hip)
+    "linear_fp8.hip": ["-Xclang", "-target-feature", "-Xclang",
+                       "-packed-fp32-ops"],
 }
 
 

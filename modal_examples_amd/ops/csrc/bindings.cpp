@@ -103,6 +103,15 @@ int moe_ffn_w4_bf16(const void*, const void*, const void*, const void*,
 int linear_w4_plan(long long, int, int, int);
 int linear_w4_bf16(const void*, const void*, const void*, float*, void*,
                    long long, int, int, int, hipStream_t);
+// linear_fp8_plan / linear_fp8_bf16: as the w4 pair, with a forced M-tile
+// count (0 = the rule) before the stream; fp8_quant_rows_bf16 returns 0 once
+// launched, non-zero (nothing launched) for an unsupported shape
+int linear_fp8_plan(long long, int, int, int);
+int fp8_quant_rows_bf16(const void*, void*, float*, long long, int,
+                        hipStream_t);
+int linear_fp8_bf16(const void*, const float*, const void*, const float*,
+                    float*, void*, long long, int, int, int, int,
+                    hipStream_t);
 // the LoRA launchers return 0 once launched, non-zero (nothing launched)
 // for a shape they do not support; lora_plan: the K-slice count of the
 // shrink GEMM (= planes of the workspace), 0 for an unsupported K
@@ -1080,6 +1089,99 @@ int64_t linear_w4_splits(int64_t M, int64_t N, int64_t K, int64_t splits) {
   return linear_w4_plan(M, (int)N, (int)K, (int)splits);
 }
 
+// ---------------------------------------------------------------- fp8 W8A8
+// Format: linear_fp8.hip.  Supported: M >= 1, N a multiple of 64, K a
+// multiple of 128; every check raises before anything is launched.
+
+// x bf16 [M,K] -> (xq float8_e4m3fn [M,K], xscale fp32 [M]): per-row dynamic
+// quantization, scale = absmax / 448 (1 for a zero row).
+std::vector<torch::Tensor> quantize_rows_fp8(torch::Tensor x) {
+  check_bf16(x, "x");
+  TORCH_CHECK(x.dim() == 2, "quantize_rows_fp8: x must be [M,K]");
+  const int64_t M = x.size(0), K = x.size(1);
+  TORCH_CHECK(M >= 1, "quantize_rows_fp8: x has no rows");
+  TORCH_CHECK(K >= 128 && K % 128 == 0, "quantize_rows_fp8: K=", K,
+              " (must be a multiple of 128)");
+  TORCH_CHECK(M < (1ll << 31) && K < (1ll << 31),
+              "quantize_rows_fp8: size out of range");
+  if ((uintptr_t)x.data_ptr() % 16) x = x.clone();  // 16 B vector loads
+  auto xq = torch::empty({M, K}, x.options().dtype(torch::kFloat8_e4m3fn));
+  auto xscale = torch::empty({M}, x.options().dtype(torch::kFloat32));
+  int rc = fp8_quant_rows_bf16(x.data_ptr(), xq.data_ptr(),
+                               xscale.data_ptr<float>(), M, (int)K,
+                               cur_stream());
+  TORCH_CHECK(rc == 0, "quantize_rows_fp8: shape not supported by the kernel "
+              "(M=", M, " K=", K, ")");
+  return {xq, xscale};
+}
+
+// xq fp8 [M,K], xscale fp32 [M], qweight fp8 [N,K], wscale fp32 [N].
+// splits = 0 takes the kernel's split rule and mtiles = 0 its M-tile rule;
+// positive values force them (tests and benchmarks only — the public op
+// never passes them).  Returns [M,N] bf16.
+torch::Tensor linear_fp8(torch::Tensor xq, torch::Tensor xscale,
+                         torch::Tensor qweight, torch::Tensor wscale,
+                         int64_t splits, int64_t mtiles) {
+  for (const auto* t : {&xq, &qweight})
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
+                    t->scalar_type() == torch::kFloat8_e4m3fn,
+                "linear_fp8: xq and qweight must be float8_e4m3fn, "
+                "contiguous, on GPU");
+  for (const auto* t : {&xscale, &wscale})
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
+                    t->scalar_type() == torch::kFloat32,
+                "linear_fp8: xscale and wscale must be fp32, contiguous, on "
+                "GPU");
+  TORCH_CHECK(xq.dim() == 2 && qweight.dim() == 2 && xscale.dim() == 1 &&
+                  wscale.dim() == 1,
+              "linear_fp8: xq must be [M,K], xscale [M], qweight [N,K], "
+              "wscale [N]");
+  const int64_t M = xq.size(0), K = xq.size(1), N = qweight.size(0);
+  TORCH_CHECK(M >= 1, "linear_fp8: xq has no rows");
+  TORCH_CHECK(K >= 128 && K % 128 == 0, "linear_fp8: K=", K,
+              " (must be a multiple of 128)");
+  TORCH_CHECK(N >= 64 && N % 64 == 0, "linear_fp8: N=", N,
+              " (must be a multiple of 64)");
+  TORCH_CHECK(qweight.size(1) == K && xscale.size(0) == M &&
+                  wscale.size(0) == N,
+              "linear_fp8: qweight ", qweight.sizes(), " / xscale ",
+              xscale.sizes(), " / wscale ", wscale.sizes(),
+              " do not match M=", M, " N=", N, " K=", K);
+  TORCH_CHECK(qweight.device() == xq.device() &&
+                  xscale.device() == xq.device() &&
+                  wscale.device() == xq.device(),
+              "linear_fp8: all tensors must be on xq's device");
+  TORCH_CHECK(M < (1ll << 31) && N < (1ll << 31) && K < (1ll << 31) &&
+                  splits >= 0 && splits < (1ll << 31) && mtiles >= 0 &&
+                  mtiles <= 2,
+              "linear_fp8: size out of range");
+  // the kernels read 16 B fragments
+  if ((uintptr_t)xq.data_ptr() % 16) xq = xq.clone();
+  if ((uintptr_t)qweight.data_ptr() % 16) qweight = qweight.clone();
+  if ((uintptr_t)wscale.data_ptr() % 16) wscale = wscale.clone();
+  const int S = linear_fp8_plan(M, (int)N, (int)K, (int)splits);
+  TORCH_CHECK(S >= 1, "linear_fp8: shape not supported by the kernel (M=", M,
+              " N=", N, " K=", K, " splits=", splits, ")");
+  auto out = torch::empty({M, N}, xq.options().dtype(torch::kBFloat16));
+  torch::Tensor ws;
+  if (S > 1) ws = torch::empty({S, M, N}, xscale.options());
+  int rc = linear_fp8_bf16(xq.data_ptr(), xscale.data_ptr<float>(),
+                           qweight.data_ptr(), wscale.data_ptr<float>(),
+                           S > 1 ? ws.data_ptr<float>() : nullptr,
+                           out.data_ptr(), M, (int)N, (int)K, (int)splits,
+                           (int)mtiles, cur_stream());
+  TORCH_CHECK(rc == 0, "linear_fp8: shape not supported by the kernel (M=", M,
+              " N=", N, " K=", K, " splits=", splits, ")");
+  return out;
+}
+
+int64_t linear_fp8_splits(int64_t M, int64_t N, int64_t K, int64_t splits) {
+  TORCH_CHECK(M < (1ll << 31) && N < (1ll << 31) && K < (1ll << 31) &&
+                  splits >= 0 && splits < (1ll << 31),
+              "linear_fp8: size out of range");
+  return linear_fp8_plan(M, (int)N, (int)K, (int)splits);
+}
+
 // ---------------------------------------------------------------- multi-LoRA
 // Supported: S <= 32 adapters, R in {16, 32, 64}, K a multiple of 64, O a
 // multiple of 128, any N.  Every check raises before anything is launched;
@@ -1419,6 +1521,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "K slices linear_w4 uses for (M, N, K); 0 = unsupported shape",
         pybind11::arg("M"), pybind11::arg("N"), pybind11::arg("K"),
         pybind11::arg("splits") = 0);
+  m.def("quantize_rows_fp8", &quantize_rows_fp8,
+        "per-row dynamic e4m3 quantization: (xq fp8 [M,K], xscale f32 [M])",
+        py::arg("x"));
+  m.def("linear_fp8", &linear_fp8,
+        "fp8 W8A8 linear: fp8 MFMA on the loaded bytes, split-K",
+        py::arg("xq"), py::arg("xscale"), py::arg("qweight"),
+        py::arg("wscale"), py::arg("splits") = 0, py::arg("mtiles") = 0);
+  m.def("linear_fp8_splits", &linear_fp8_splits,
+        "K slices linear_fp8 uses for (M, N, K); 0 = unsupported shape",
+        py::arg("M"), py::arg("N"), py::arg("K"), py::arg("splits") = 0);
   m.def("lora_schedule", &lora_schedule,
         "multi-LoRA row schedule: rows grouped by adapter into 32-row tiles",
         py::arg("idx"), py::arg("slots"));

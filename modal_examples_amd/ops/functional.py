@@ -978,3 +978,132 @@ def linear_w4(x, qweight, scales):
         return ref.linear_w4_ref(x, qweight, scales)
     y = ext.linear_w4(x.reshape(-1, K).contiguous(), qweight, scales)
     return y.view(*x.shape[:-1], N)
+
+
+# ---- fp8 W8A8 linear.  Supported shapes (csrc/linear_fp8.hip): K a multiple
+# of 128, N a multiple of 64, any number of rows >= 1, contiguous weights.
+# As for int4, the checks run on every device, before the dispatch.
+
+def _check_fp8_weight(qweight, wscale):
+    """Returns (N, K) of a quantized weight."""
+    if qweight.dtype is not torch.float8_e4m3fn:
+        raise TypeError(f"qweight must be float8_e4m3fn, got {qweight.dtype}")
+    if wscale.dtype is not torch.float32:
+        raise TypeError(f"wscale must be fp32, got {wscale.dtype}")
+    if qweight.dim() != 2 or wscale.dim() != 1:
+        raise ValueError(f"qweight must be [N, K] and wscale [N], got "
+                         f"{tuple(qweight.shape)}, {tuple(wscale.shape)}")
+    N, K = qweight.shape
+    if K < 128 or K % 128 != 0:
+        raise ValueError(f"qweight has K={K} (must be a multiple of 128)")
+    if N < 64 or N % 64 != 0:
+        raise ValueError(f"qweight has N={N} (must be a multiple of 64)")
+    if wscale.shape[0] != N:
+        raise ValueError(f"wscale must be [N={N}], got {tuple(wscale.shape)}")
+    if wscale.device != qweight.device:
+        raise ValueError(f"wscale is on {wscale.device}, qweight on "
+                         f"{qweight.device}")
+    for name, t in (("qweight", qweight), ("wscale", wscale)):
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    return N, K
+
+
+def _check_fp8_x(x, K, qweight):
+    if not x.is_floating_point() or x.dtype is torch.float8_e4m3fn:
+        raise TypeError(f"x must be bf16 or wider floating point, got "
+                        f"{x.dtype}")
+    if x.dim() < 1 or x.shape[-1] != K:
+        raise ValueError(f"x must be [..., K={K}], got {tuple(x.shape)}")
+    if x.numel() == 0:
+        raise ValueError(f"x has no rows: {tuple(x.shape)}")
+    if qweight is not None and x.device != qweight.device:
+        raise ValueError(f"x is on {x.device}, qweight on {qweight.device}")
+
+
+def quantize_fp8(weight):
+    """weight [N, K] (bf16 or fp32) -> (qweight float8_e4m3fn [N, K], wscale
+    fp32 [N]): symmetric e4m3 quantization with one scale per output
+    channel, done offline in torch ops.
+
+    scale = absmax(row) / 448, 1 for an all-zero row; q = rne_e4m3(w / scale);
+    the dequantized weight is wscale[n] * float(q[n, k])."""
+    _check_w4_weight(weight)   # the same shapes and dtypes as int4
+    return ref.quantize_fp8_ref(weight)
+
+
+def dequantize_fp8(qweight, wscale):
+    """The dequantized weight wscale[n] * float(q[n, k]), fp32 [N, K]."""
+    _check_fp8_weight(qweight, wscale)
+    return ref.dequantize_fp8_ref(qweight, wscale)
+
+
+def quantize_rows_fp8(x):
+    """x [..., K] -> (xq float8_e4m3fn [..., K], xscale fp32 [...]):
+    per-row (per-token) dynamic quantization, scale = absmax(row) / 448, 1
+    for a zero row, q = rne_e4m3(x / scale) with both divisions in fp32.
+
+    On the GPU in bf16 this is fp8_quant_rows_kernel (csrc/linear_fp8.hip),
+    one workgroup per row, x read once; elsewhere the torch reference, which
+    the kernel matches bit for bit."""
+    _check_fp8_x(x, x.shape[-1] if x.dim() else 0, None)
+    K = x.shape[-1]
+    if K < 128 or K % 128 != 0:
+        raise ValueError(f"x has K={K} (must be a multiple of 128)")
+    ext = _ext_for(x)
+    if ext is None:
+        return ref.quantize_rows_fp8_ref(x)
+    xq, xs = ext.quantize_rows_fp8(x.reshape(-1, K).contiguous())
+    return xq.view(x.shape), xs.view(x.shape[:-1])
+
+
+def linear_fp8_q(xq, xscale, qweight, wscale):
+    """The GEMM of `linear_fp8` alone: xq float8_e4m3fn [M, K] with xscale
+    fp32 [M] (quantize_rows_fp8) against qweight / wscale (quantize_fp8),
+    y[m, n] = bf16((sum_k xq[m,k] * qweight[n,k]) * xscale[m] * wscale[n]),
+    [M, N] bf16.  On the GPU fp8_gemm_kernel; elsewhere the same arithmetic
+    in torch ops."""
+    N, K = _check_fp8_weight(qweight, wscale)
+    if xq.dtype is not torch.float8_e4m3fn:
+        raise TypeError(f"xq must be float8_e4m3fn, got {xq.dtype}")
+    if xscale.dtype is not torch.float32:
+        raise TypeError(f"xscale must be fp32, got {xscale.dtype}")
+    if xq.dim() != 2 or xq.shape[1] != K:
+        raise ValueError(f"xq must be [M, K={K}], got {tuple(xq.shape)}")
+    M = xq.shape[0]
+    if M == 0:
+        raise ValueError(f"xq has no rows: {tuple(xq.shape)}")
+    if tuple(xscale.shape) != (M,):
+        raise ValueError(f"xscale must be [M={M}], got "
+                         f"{tuple(xscale.shape)}")
+    for name, t in (("xq", xq), ("xscale", xscale)):
+        if t.device != qweight.device:
+            raise ValueError(f"{name} is on {t.device}, qweight on "
+                             f"{qweight.device}")
+    if not xq.is_cuda:
+        return ref.linear_fp8_q_ref(xq, xscale, qweight, wscale)
+    ext = _sync_wrapped(get_ext(required=True))
+    return ext.linear_fp8(xq.contiguous(), xscale.contiguous(), qweight,
+                          wscale)
+
+
+def linear_fp8(x, qweight, wscale):
+    """x [..., K] . w_hat^T with fp8 weights (quantize_fp8) and x quantized
+    per row at run time ("W8A8 dynamic"), K2f.
+
+    On the GPU in bf16 without grad this is `quantize_rows_fp8` followed by
+    the csrc/linear_fp8.hip GEMM: the fp8 bytes are the MFMA operands as
+    loaded, the two scales multiply the fp32 sum, one rounding to bf16; K is
+    split deterministically, the result of a row is bitwise reproducible
+    and independent of the other rows, and the call captures into a graph.
+    Anywhere else it is the reference composition on the same device
+    (quantize rows, dequantize both, `linear`).  Returns [..., N] in x's
+    dtype."""
+    N, K = _check_fp8_weight(qweight, wscale)
+    _check_fp8_x(x, K, qweight)
+    ext = _ext_for(x)
+    if ext is None:
+        return ref.linear_fp8_ref(x, qweight, wscale)
+    xq, xs = ext.quantize_rows_fp8(x.reshape(-1, K).contiguous())
+    y = ext.linear_fp8(xq, xs, qweight, wscale)
+    return y.view(*x.shape[:-1], N)

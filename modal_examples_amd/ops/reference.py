@@ -606,6 +606,88 @@ def linear_w4_bound_ref(x, qweight, scales, bf16_points=False):
     return want, tol
 
 
+# ---- fp8 W8A8 linear.  Format (csrc/linear_fp8.hip): qweight
+# float8_e4m3fn [N, K] with one fp32 scale per output channel, activations
+# quantized per row at run time; both scales are absmax / 448.
+
+FP8_MAX = 448.0
+
+
+def _quantize_fp8_lastdim(t):
+    """t [..., K] -> (q float8_e4m3fn [..., K], scale fp32 [...]), the
+    arithmetic the row-quantization kernel is pinned to: scale = amax / 448
+    as an fp32 division, 1 where amax is 0; q = rne_e4m3(float(t) / scale),
+    an fp32 division.  The clamp changes no finite value (the quotient is at
+    most 448 * (1 + 2^-22), which rounds to 448); it keeps the cast away
+    from NaN, e4m3fn's only out-of-range encoding."""
+    w = t.detach().float()
+    scale = w.abs().amax(-1) / FP8_MAX
+    scale = torch.where(scale == 0, torch.ones_like(scale), scale)
+    q = (w / scale.unsqueeze(-1)).clamp(-FP8_MAX, FP8_MAX)
+    return q.to(torch.float8_e4m3fn), scale
+
+
+def quantize_fp8_ref(weight):
+    """weight [N, K] -> (qweight float8_e4m3fn [N, K], wscale fp32 [N]),
+    one scale per output channel."""
+    return _quantize_fp8_lastdim(weight)
+
+
+def quantize_rows_fp8_ref(x):
+    """x [..., K] -> (xq float8_e4m3fn [..., K], xscale fp32 [...]), one
+    scale per row; for bf16 x bit for bit what fp8_quant_rows_kernel
+    writes."""
+    return _quantize_fp8_lastdim(x)
+
+
+def dequantize_fp8_ref(q, scale):
+    """fp32 [..., K] = scale[..., None] * float(q), one fp32 rounding per
+    element (an e4m3 value times an fp32 scale can need 27 bits)."""
+    return q.float() * scale.unsqueeze(-1)
+
+
+def linear_fp8_q_ref(xq, xscale, qweight, wscale):
+    """[M, N] bf16: the fp32 product of the fp8 values, then
+    (acc * xscale[m]) * wscale[n] and one rounding, the kernel's order."""
+    acc = xq.float() @ qweight.float().T
+    return ((acc * xscale.unsqueeze(-1)) * wscale).to(torch.bfloat16)
+
+
+def linear_fp8_ref(x, qweight, wscale):
+    """x [..., K] . w_hat^T with x quantized per row: both sides are
+    dequantized, cast to x's dtype and go through `linear`.  The gradient
+    passes the row quantization straight through to x."""
+    xq, xscale = quantize_rows_fp8_ref(x)
+    xh = dequantize_fp8_ref(xq, xscale).to(x.dtype)
+    if x.requires_grad:
+        xh = x + (xh - x).detach()
+    w = dequantize_fp8_ref(qweight, wscale).to(x.dtype)
+    return torch.nn.functional.linear(xh, w)
+
+
+def linear_fp8_bound_ref(xq, xscale, qweight, wscale):
+    """(want, tol) in fp64, [M, N], for an implementation that multiplies
+    the fp8 values exactly, accumulates in fp32, applies the two scales to
+    the fp32 sum and rounds the output to bf16 once.
+
+      want   (xq . qweight^T) * xscale[m] * wscale[n]
+      A      (|xq| . |qweight|^T) * xscale[m] * wscale[n]
+      tol    2^-7 * |want| + 2^-10 * A
+
+    linear_w4_bound_ref's derivation: the bf16 rounding moves the output by
+    at most 2^-8 * |want| and the first term is twice that; worst-case fp32
+    accumulation is about K * 2^-24 * A, at most 2^-10 * A up to K = 16384
+    (the two fp32 scale products add 2^-23 * |want|, far inside the first
+    term)."""
+    a = xq.detach().cpu().double()
+    w = qweight.detach().cpu().double()
+    sc = xscale.detach().cpu().double().unsqueeze(-1) \
+        * wscale.detach().cpu().double()
+    want = (a @ w.T) * sc
+    A = (a.abs() @ w.abs().T) * sc
+    return want, 2.0 ** -7 * want.abs() + 2.0 ** -10 * A
+
+
 # ---- multi-LoRA delta (csrc/lora.hip).  bank_a [S, R, K], bank_b [S, O, R]
 # with alpha / r folded into bank_b; idx [N] picks a row's adapter, an id
 # outside [0, S) means "no adapter".

@@ -14,7 +14,15 @@ call and the arm's own weight bytes over that time.
 --sweep adds, per shape, the kernel under forced split counts (the binding's
 test-only argument): the data behind the split rule.
 
-Usage: python scripts/bench_linear_w4.py [--rows 1 8 32] [--sweep] [--out F]
+--fp8 adds the fp8 W8A8 arms (csrc/linear_fp8.hip) to the same alternating
+windows: "fp8", the public op ops.linear_fp8 (row quantization + GEMM);
+"fp8gemm", the GEMM alone on rows quantized beforehand; "fp8deq", the
+dequantize-then-GEMM lane of Fp8Linear.  With --sweep it also times the fp8
+GEMM under forced split counts (M = 1, 32) and with one against two M-tiles
+per wave (M >= 64).
+
+Usage: python scripts/bench_linear_w4.py [--rows 1 8 32] [--sweep] [--fp8]
+                                         [--out F]
 """
 import argparse
 import os
@@ -83,7 +91,44 @@ def time_graphs(graphs):
             for n, s in samples.items()}
 
 
-def bench_shape(name, N, K, rows, sweep, out):
+def fp8_arms(ext, OF, name, N, K, M, x, fq, fs, sweep, out):
+    """The fp8 graphs of one (shape, M), and the sweep lines."""
+    Rf = len(fq)
+    xq, xs = OF.quantize_rows_fp8(x)
+
+    def deq(i):
+        w = OF.dequantize_fp8(fq[i], fs[i]).to(torch.bfloat16)
+        return torch.nn.functional.linear(x, w)
+
+    graphs = {
+        "fp8": (capture(lambda i: OF.linear_fp8(x, fq[i], fs[i]), Rf), Rf),
+        "fp8gemm": (capture(
+            lambda i: ext.linear_fp8(xq, xs, fq[i], fs[i]), Rf), Rf),
+        "fp8deq": (capture(deq, 2), 2),
+    }
+    if not sweep:
+        return graphs
+    if M in (1, 32):
+        nch = K // 128
+        cands = sorted({min(nch, max(1, -(-t // (N // 64))))
+                        for t in (128, 256, 512, 1024, 2048, 4096)})
+        sg = {f"S={s}": (capture(
+            lambda i, s=s: ext.linear_fp8(xq, xs, fq[i], fs[i], s), Rf), Rf)
+            for s in cands}
+        out(f"{name:8s} M={M:4d} fp8 gemm splits sweep: " + "  ".join(
+            f"{n} ({int(n[2:]) * (N // 64)} waves) {v[0]:.1f} us"
+            for n, v in time_graphs(sg).items()))
+    if M >= 64:
+        mg = {f"MT={t}": (capture(
+            lambda i, t=t: ext.linear_fp8(xq, xs, fq[i], fs[i], 0, t), Rf), Rf)
+            for t in (1, 2)}
+        out(f"{name:8s} M={M:4d} fp8 gemm one vs two M-tiles: " + "  ".join(
+            f"{n} {v[0]:.1f} us [{v[1]:.1f}..{v[2]:.1f}]"
+            for n, v in time_graphs(mg).items()))
+    return graphs
+
+
+def bench_shape(name, N, K, rows, sweep, out, fp8=False):
     from modal_examples_amd.ops import functional as OF
     from modal_examples_amd.ops._build import get_ext
 
@@ -99,6 +144,14 @@ def bench_shape(name, N, K, rows, sweep, out):
     out(f"## {name}: N={N} K={K}; int4 {w4_bytes(N, K) / 1e6:.1f} MB x {Rq} "
         f"copies, bf16 {2 * N * K / 1e6:.1f} MB x {Rb} copies; split rule "
         f"S={ext.linear_w4_splits(1, N, K)}")
+    if fp8:
+        Rf = copies_for(N * K + 4 * N)
+        fq = [(100 * torch.randn(N, K, device="cuda", generator=gen)
+               ).clamp_(-448, 448).to(torch.float8_e4m3fn) for _ in range(Rf)]
+        fs = [1e-4 * (1 + torch.rand(N, device="cuda", generator=gen))
+              for _ in range(Rf)]
+        out(f"## {name}: fp8 {(N * K + 4 * N) / 1e6:.1f} MB x {Rf} copies; "
+            f"split rule S={ext.linear_fp8_splits(1, N, K)}")
     with torch.no_grad():
         for M in rows:
             x = torch.randn(M, K, device="cuda", generator=gen).to(torch.bfloat16)
@@ -113,15 +166,22 @@ def bench_shape(name, N, K, rows, sweep, out):
                     lambda i: torch.nn.functional.linear(x, wb[i]), Rb), Rb),
                 "dequant": (capture(deq, 2), 2),
             }
+            if fp8:
+                graphs.update(fp8_arms(ext, OF, name, N, K, M, x, fq, fs,
+                                       sweep, out))
             res = time_graphs(graphs)
             nbytes = {"w4": w4_bytes(N, K), "bf16": 2 * N * K,
                       "dequant": w4_bytes(N, K)}
+            nbytes.update({n: N * K + 4 * N for n in res if n[:3] == "fp8"})
             line = f"{name:8s} M={M:4d}"
-            for n in ("w4", "bf16", "dequant"):
+            for n in res:
                 med, lo, hi = res[n]
                 line += (f" | {n} {med:8.1f} us [{lo:.1f}..{hi:.1f}] "
                          f"{nbytes[n] / med / 1e3:7.1f} GB/s")
             line += f" | bf16/w4 {res['bf16'][0] / res['w4'][0]:.2f}x"
+            if fp8:
+                line += (f" bf16/fp8 {res['bf16'][0] / res['fp8'][0]:.2f}x"
+                         f" w4/fp8 {res['w4'][0] / res['fp8'][0]:.2f}x")
             out(line)
             del graphs
             if sweep and M in (1, 32):
@@ -137,6 +197,8 @@ def bench_shape(name, N, K, rows, sweep, out):
                     for n, v in sres.items()))
                 del sg
     del qw, sc, wb
+    if fp8:
+        del fq, fs
     torch.cuda.empty_cache()
 
 
@@ -145,6 +207,7 @@ def main():
     ap.add_argument("--rows", type=int, nargs="+", default=list(ROWS))
     ap.add_argument("--shapes", nargs="+", default=[s[0] for s in SHAPES])
     ap.add_argument("--sweep", action="store_true")
+    ap.add_argument("--fp8", action="store_true")
     ap.add_argument("--out", default=None, help="also append the lines here")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -161,7 +224,7 @@ def main():
         f">= {ROTATE_BYTES >> 20} MB; GB/s = the arm's weight bytes / time")
     for name, N, K in SHAPES:
         if name in a.shapes:
-            bench_shape(name, N, K, a.rows, a.sweep, out)
+            bench_shape(name, N, K, a.rows, a.sweep, out, a.fp8)
 
 
 if __name__ == "__main__":

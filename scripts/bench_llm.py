@@ -25,9 +25,10 @@ def main():
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--small", action="store_true")
     ap.add_argument("--kv-dtype", choices=("bf16", "fp8"), default="bf16")
-    ap.add_argument("--weight-dtype", choices=("bf16", "int4"),
+    ap.add_argument("--weight-dtype", choices=("bf16", "int4", "fp8"),
                     default="bf16",
-                    help="int4: 4-bit block projections (ops.linear_w4)")
+                    help="int4: 4-bit block projections (ops.linear_w4); "
+                         "fp8: e4m3 W8A8 projections (ops.linear_fp8)")
     ap.add_argument("--spec", type=int, default=0,
                     help="ngram speculative tokens (eager decode path)")
     ap.add_argument("--prefix-cache", action="store_true")

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Decompose the Llama decode step: graph replay vs full engine.step.
 
-Usage: bench_llm_step.py [BATCH] [--weight-dtype bf16|int4]"""
+Usage: bench_llm_step.py [BATCH] [--weight-dtype bf16|int4|fp8]"""
 import argparse
 import os
 import sys
@@ -18,7 +18,7 @@ from modal_examples_amd.models.llama.model import LlamaConfig  # noqa: E402
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("batch", type=int, nargs="?", default=64)
-    ap.add_argument("--weight-dtype", choices=("bf16", "int4"),
+    ap.add_argument("--weight-dtype", choices=("bf16", "int4", "fp8"),
                     default="bf16")
     args = ap.parse_args()
     batch = args.batch

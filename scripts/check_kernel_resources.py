@@ -70,6 +70,13 @@ OCCUPANCY_FLOORS = {
     "moe_gemm_w4_kernelILb1E": 2,    # up GEMM
     "moe_gemm_w4_kernelILb0E": 2,    # down GEMM, one K slice per wave
     "moe_combine_planes_kernel": 8,
+    # fp8_gemm_kernel<MT>: two register sets of a 128-deep chunk (48 / 64
+    # registers each for MT = 1 / 2) beside 32 / 64 accumulators; two waves
+    # per SIMD, the second hides a chunk's load latency as in w4_gemm_kernel
+    "fp8_gemm_kernelILi1E": 2,
+    "fp8_gemm_kernelILi2E": 2,
+    "fp8_reduce_kernel": 8,
+    "fp8_quant_rows_kernel": 8,   # both: row in registers, row read twice
 }
 
 
