@@ -56,6 +56,14 @@ class RMSNormK(nn.Module, _F32ParamCache):
         return OF.rmsnorm(x, self._f32("weight"), self.eps)
 
 
+# GroupNorm statistics from the producing conv's epilogue: Conv3x3 hands them
+# out (forward(..., gn_groups=G)) and the models pass them to the GroupNormSiLU
+# that reads the conv's output.  False makes every Conv3x3 return None for
+# them, so each norm takes its own statistics pass (the A/B switch of the
+# wiring tests).
+GN_STATS_FROM_CONV = True
+
+
 class GroupNormSiLU(nn.Module, _F32ParamCache):
     """Fused GroupNorm(+SiLU) NCHW via the gfx950 kernel."""
 
@@ -68,12 +76,14 @@ class GroupNormSiLU(nn.Module, _F32ParamCache):
         self.eps = eps
         self.silu = silu
 
-    def forward(self, x, out_nhwc: bool = False):
+    def forward(self, x, out_nhwc: bool = False, stats=None):
         """out_nhwc=True returns [B, H*W, C] (the kernel writes that layout
-        itself) for the sequence-major sections that follow a GroupNorm."""
+        itself) for the sequence-major sections that follow a GroupNorm.
+        stats: what the Conv3x3 that produced x returned for gn_groups =
+        self.groups (None: the statistics are computed here)."""
         return OF.groupnorm_silu(x, self._f32("weight"), self._f32("bias"),
                                  self.groups, self.eps, self.silu,
-                                 out_nhwc=out_nhwc)
+                                 out_nhwc=out_nhwc, stats=stats)
 
 
 class Conv3x3(nn.Conv2d):
@@ -110,21 +120,40 @@ class Conv3x3(nn.Conv2d):
             return False
         return True
 
-    def forward_gn(self, x, gn, residual=None, upsample: bool = False):
+    def forward_gn(self, x, gn, residual=None, upsample: bool = False,
+                   stats=None):
         """Fused GroupNorm+SiLU -> conv (gn: a GroupNormSiLU module with
-        silu=True).  Falls back to gn(x) then conv off the kernel path."""
+        silu=True; stats as in GroupNormSiLU.forward).  Falls back to gn(x)
+        then conv off the kernel path."""
         if self._use_kernel(x) and gn.silu:
             wr, b = self._packed()
             return OF.conv3x3_gn(x, wr, b, self.out_channels,
                                  gn._f32("weight"), gn._f32("bias"),
                                  gn.groups, gn.eps, residual=residual,
-                                 raw_weight=self.weight, upsample=upsample)
-        return self.forward(gn(x), residual=residual, upsample=upsample)
+                                 raw_weight=self.weight, upsample=upsample,
+                                 stats=stats)
+        return self.forward(gn(x, stats=stats), residual=residual,
+                            upsample=upsample)
 
-    def forward(self, x, residual=None, upsample: bool = False, addend=None):
+    def forward(self, x, residual=None, upsample: bool = False, addend=None,
+                gn_groups=None):
         """addend [N, K]: one value per (image, output channel), added to the
         conv output in the kernel's epilogue (the resnets' time-embedding
-        projection); a plain broadcast add off the kernel path."""
+        projection); a plain broadcast add off the kernel path.
+
+        gn_groups=G (the group count of the GroupNormSiLU that reads the
+        result) returns (y, stats): the kernel's epilogue takes the norm's
+        statistics while it writes y.  stats is None wherever it takes none
+        (training, CPU, fp32, G not dividing the channels into quads);
+        GroupNormSiLU accepts either."""
+        if gn_groups is not None:
+            if self._use_kernel(x) and GN_STATS_FROM_CONV:
+                wr, b = self._packed()
+                return OF.conv3x3(x, wr, b, self.out_channels,
+                                  residual=residual, raw_weight=self.weight,
+                                  upsample=upsample, addend=addend,
+                                  gn_groups=gn_groups)
+            return self.forward(x, residual, upsample, addend), None
         if self._use_kernel(x):
             wr, b = self._packed()
             return OF.conv3x3(x, wr, b, self.out_channels, residual=residual,

@@ -66,14 +66,20 @@ class ResnetBlock(nn.Module):
         self.conv2 = Conv3x3(c_out, c_out)
         self.skip = Conv1x1(c_in, c_out) if c_in != c_out else nn.Identity()
 
-    def forward(self, x, temb):
-        # GN+SiLU stays a separate two-pass kernel: fusing it into conv
-        # staging re-runs the exp per output-k-tile (measured 13.3->9.4 img/s).
+    def forward(self, x, temb, stats=None, gn_groups=None):
+        """stats: norm1's statistics of x from the conv that produced x.
+        gn_groups: the group count of the norm that reads the result; the
+        return value is then (y, stats of y) (see Conv3x3.forward)."""
+        # GN+SiLU stays a separate kernel: fusing it into conv staging
+        # re-runs the exp per output-k-tile (measured 13.3->9.4 img/s).
         # The time-embedding projection, one value per (image, channel), is
-        # added in conv1's epilogue: no pass over h between conv1 and norm2.
+        # added in conv1's epilogue: no pass over h between conv1 and norm2,
+        # whose statistics that epilogue takes as well.
         t = self.temb_proj(torch.nn.functional.silu(temb))
-        h = self.conv1(self.norm1(x), addend=t)
-        return self.conv2(self.norm2(h), residual=self.skip(x))
+        h, s = self.conv1(self.norm1(x, stats=stats), addend=t,
+                          gn_groups=self.norm2.groups)
+        return self.conv2(self.norm2(h, stats=s), residual=self.skip(x),
+                          gn_groups=gn_groups)
 
 
 class SpatialTransformer(nn.Module):
@@ -92,8 +98,8 @@ class SpatialTransformer(nn.Module):
         )
         self.proj_out = nn.Linear(channels, channels)
 
-    def forward(self, x, ctx):
-        h = self.proj_in(self.norm(x, out_nhwc=True))
+    def forward(self, x, ctx, stats=None):
+        h = self.proj_in(self.norm(x, out_nhwc=True, stats=stats))
         for blk in self.blocks:
             h = blk(h, ctx)
         return OF.add_nhwc_to_nchw(x, self.proj_out(h))
@@ -198,28 +204,33 @@ class UNetXL(nn.Module):
         temb = self.time_mlp(timestep_embedding(t, self.cfg.channels[0]).to(dt))
         temb = temb + self.add_mlp(pooled_add)
 
-        h = self.conv_in(x)
+        # s: the GroupNorm statistics of h from the conv that wrote it, None
+        # once anything else (transformer, downsample, cat) has produced h
+        G = self.norm_out.groups  # every GroupNorm here has the same count
+        h, s = self.conv_in(x, gn_groups=G)
         skips = [h]
         for lvl, blocks in enumerate(self.down_blocks):
             for entry in blocks:
-                h = entry["resnet"](h, temb)
+                h, s = entry["resnet"](h, temb, stats=s, gn_groups=G)
                 if "attn" in entry:
-                    h = entry["attn"](h, ctx)
+                    h, s = entry["attn"](h, ctx, stats=s), None
                 skips.append(h)
             if not isinstance(self.downsamplers[lvl], nn.Identity):
-                h = self.downsamplers[lvl](h)
+                h, s = self.downsamplers[lvl](h), None
                 skips.append(h)
 
-        h = self.mid_res1(h, temb)
-        h = self.mid_attn(h, ctx)
+        h, s = self.mid_res1(h, temb, stats=s, gn_groups=G)
+        h = self.mid_attn(h, ctx, stats=s)
         h = self.mid_res2(h, temb)
 
         for i, blocks in enumerate(self.up_blocks):
             for entry in blocks:
                 h = torch.cat([h, skips.pop()], dim=1)
-                h = entry["resnet"](h, temb)
                 if "attn" in entry:
-                    h = entry["attn"](h, ctx)
+                    h, s = entry["resnet"](h, temb, gn_groups=G)
+                    h = entry["attn"](h, ctx, stats=s)
+                else:
+                    h = entry["resnet"](h, temb)
             if not isinstance(self.upsamplers[i], nn.Identity):
                 h = self.upsamplers[i](h)
 

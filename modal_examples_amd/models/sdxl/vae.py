@@ -29,14 +29,20 @@ class VAEResnet(nn.Module):
         self.conv2 = Conv3x3(c_out, c_out)
         self.skip = Conv1x1(c_in, c_out) if c_in != c_out else nn.Identity()
 
-    def forward(self, x):
+    def forward(self, x, stats=None, gn_groups=None):
+        """stats: norm1's statistics of x from the conv that produced x.
+        gn_groups: the group count of the norm that reads the result; the
+        return value is then (y, stats of y) (see Conv3x3.forward)."""
         # conv2 fuses the skip add (K3 epilogue).  NOTE measured negative
         # result: fusing GN+SiLU INTO conv staging (conv3x3_gn) regressed the
         # step 13.3->9.4 img/s — every output-k-tile re-reads the input, so
         # the fused exp recomputes K/64 times per element.  The separate
-        # two-pass GN kernel stays the fast path.
-        h = self.conv1(self.norm1(x))
-        return self.conv2(self.norm2(h), residual=self.skip(x))
+        # apply kernel stays the fast path; its statistics come from the
+        # epilogue of the conv before it.
+        h, s = self.conv1(self.norm1(x, stats=stats),
+                          gn_groups=self.norm2.groups)
+        return self.conv2(self.norm2(h, stats=s), residual=self.skip(x),
+                          gn_groups=gn_groups)
 
 
 class VAEMidAttention(nn.Module):
@@ -52,8 +58,9 @@ class VAEMidAttention(nn.Module):
         self.chunk = chunk
         self.scale = c ** -0.5
 
-    def forward(self, x):
-        h = self.norm(x, out_nhwc=True)  # [B, HW, C] straight from the kernel
+    def forward(self, x, stats=None):
+        # [B, HW, C] straight from the kernel
+        h = self.norm(x, out_nhwc=True, stats=stats)
         q, k, v = self.q(h), self.k(h), self.v(h)
         outs = []
         for i in range(0, q.shape[1], self.chunk):
@@ -87,14 +94,19 @@ class VAEDecoder(nn.Module):
         self.conv_out = Conv3x3(channels[-1], out_channels)
 
     def forward(self, z):
-        h = self.conv_in(z / self.scaling_factor)
-        h = self.mid_res2(self.mid_attn(self.mid_res1(h)))
+        # s: the statistics of h for the GroupNorm that reads it next, from
+        # the conv that wrote h.  Only mid_res2 follows something else (the
+        # transposing add of the attention).
+        G = self.norm_out.groups  # every GroupNorm here has the same count
+        h, s = self.conv_in(z / self.scaling_factor, gn_groups=G)
+        h, s = self.mid_res1(h, stats=s, gn_groups=G)
+        h, s = self.mid_res2(self.mid_attn(h, stats=s), gn_groups=G)
         for blocks, ups in self.levels:
             for blk in blocks:
-                h = blk(h)
-            if len(ups):
-                h = ups[0](h, upsample=True)  # fused nearest-2x + conv
-        return self.conv_out(self.norm_out(h))
+                h, s = blk(h, stats=s, gn_groups=G)
+            if len(ups):  # fused nearest-2x + conv
+                h, s = ups[0](h, upsample=True, gn_groups=G)
+        return self.conv_out(self.norm_out(h, stats=s))
 
 
 class VAEDecoderSmall(VAEDecoder):

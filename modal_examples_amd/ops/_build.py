@@ -46,6 +46,10 @@ EXTRA_FLAGS = {
                                     "-packed-fp32-ops"],
     "lora.hip": ["-Xclang", "-target-feature", "-Xclang",
                  "-packed-fp32-ops"],
+    # the epilogue's statistics are pairs of independent fp32 adds and fmas
+    # that the compiler would otherwise pair up
+    "conv3x3.hip": ["-Xclang", "-target-feature", "-Xclang",
+                    "-packed-fp32-ops"],
     # no fast-math flag may join these: fp8_quant_rows_kernel's fp32
     # divisions must stay correctly rounded (csrc/linear_fp8.hip)
     "linear_fp8.hip": ["-Xclang", "-target-feature", "-Xclang",

@@ -38,10 +38,12 @@ int paged_decode_packed_bf16(const void*, const void*, const void*, const int*,
                              int, hipStream_t);
 void groupnorm_silu_bf16(const void*, void*, float*, const float*,
                          const float*, int, int, long long, int, float, int,
-                         hipStream_t);
+                         int, hipStream_t);
 void groupnorm_silu_nhwc_bf16(const void*, void*, float*, const float*,
                               const float*, int, int, long long, int, float,
-                              int, hipStream_t);
+                              int, int, hipStream_t);
+void gn_stats_finalize(const float*, float*, int, int, int, int, int,
+                       hipStream_t);
 void layernorm_bf16(const void*, void*, const float*, const float*, long long,
                     int, float, hipStream_t);
 void add_layernorm_bf16(const void*, const void*, void*, void*, const float*,
@@ -78,11 +80,12 @@ void cfg_euler_dev_bf16(const void*, const void*, const void*, void*,
                         hipStream_t);
 void advance_step(long long*, hipStream_t);
 void conv3x3_bf16(const void*, const void*, const void*, const void*,
-                  const void*, void*, const float*, const float*, int, int,
-                  int, int, int, int, int, int, hipStream_t);
+                  const void*, void*, const float*, const float*, float*, int,
+                  int, int, int, int, int, int, int, hipStream_t);
+void conv3x3_stats_dims(int, int, int, int*, int*);
 void gn_conv_coeffs_bf16(const void*, float*, const float*, const float*,
                          float*, float*, int, int, int, long long, int, float,
-                         hipStream_t);
+                         int, hipStream_t);
 // the MoE launchers return 0 once launched, non-zero (nothing launched)
 // for a shape they do not support
 int moe_max_tiles(long long, int, int);
@@ -517,20 +520,44 @@ void attention_bwd(torch::Tensor q, torch::Tensor k, torch::Tensor v,
 
 // ---------------------------------------------------------------- norms
 
+// The (sum, sumsq) workspace of a GroupNorm over x: the caller's statistics
+// (conv3x3_stats wrote them for exactly this tensor), checked, or zeros for
+// gn_partial_kernel to add into.
+torch::Tensor gn_sums(const char* op, const torch::Tensor& x, int64_t groups,
+                      const c10::optional<torch::Tensor>& stats) {
+  const int64_t N = x.size(0), C = x.size(1);
+  auto fopt = x.options().dtype(torch::kFloat32);
+  if (!stats.has_value()) return torch::zeros({N * groups * 2}, fopt);
+  TORCH_CHECK(groups >= 1 && C % groups == 0 && (C / groups) % 4 == 0, op,
+              ": statistics need groups that divide C into a multiple of 4 "
+              "channels, got groups=", groups, " C=", C);
+  TORCH_CHECK(stats->device() == x.device(), op, ": stats is on ",
+              stats->device(), ", x on ", x.device());
+  TORCH_CHECK(stats->scalar_type() == torch::kFloat && stats->is_contiguous(),
+              op, ": stats must be fp32 and contiguous");
+  TORCH_CHECK(stats->dim() == 3 && stats->size(2) == 2, op,
+              ": stats must be [N, groups, 2], got ", stats->sizes());
+  TORCH_CHECK(stats->size(1) == groups, op, ": stats were taken for ",
+              stats->size(1), " groups, the norm has ", groups);
+  TORCH_CHECK(stats->size(0) == N, op, ": stats were taken for ",
+              stats->size(0), " images, x has ", N);
+  return *stats;
+}
+
 torch::Tensor groupnorm_silu(torch::Tensor x, torch::Tensor gamma,
                              torch::Tensor beta, int64_t groups, double eps,
-                             bool do_silu) {
+                             bool do_silu,
+                             c10::optional<torch::Tensor> stats) {
   check_bf16(x, "x");
   TORCH_CHECK(x.dim() == 4, "x must be NCHW");
   int N = x.size(0), C = x.size(1);
   long long HW = (long long)x.size(2) * x.size(3);
   auto y = torch::empty_like(x);
-  auto ws = torch::zeros({N * groups * 2},
-                         x.options().dtype(torch::kFloat32));
+  auto ws = gn_sums("groupnorm_silu", x, groups, stats);
   groupnorm_silu_bf16(x.data_ptr(), y.data_ptr(), ws.data_ptr<float>(),
                       gamma.data_ptr<float>(), beta.data_ptr<float>(), N, C,
                       HW, (int)groups, (float)eps, do_silu ? 1 : 0,
-                      cur_stream());
+                      stats.has_value() ? 1 : 0, cur_stream());
   return y;
 }
 
@@ -567,7 +594,8 @@ void check_same_device(const char* op, const torch::Tensor& a,
 // without the transposing copy.  Everything is checked before the launch.
 torch::Tensor groupnorm_silu_nhwc(torch::Tensor x, torch::Tensor gamma,
                                   torch::Tensor beta, int64_t groups,
-                                  double eps, bool do_silu) {
+                                  double eps, bool do_silu,
+                                  c10::optional<torch::Tensor> stats) {
   const char* op = "groupnorm_silu_nhwc";
   check_bf16(x, "x");
   TORCH_CHECK(x.dim() == 4, op, ": x must be NCHW, got ", x.dim(), " dims");
@@ -585,11 +613,12 @@ torch::Tensor groupnorm_silu_nhwc(torch::Tensor x, torch::Tensor gamma,
               op, ": too large for the kernel (N <= 65535, H*W < 2^31, "
               "C < 2^22, N*groups < 2^20), got x ", x.sizes());
   auto y = torch::empty({N, HW, C}, x.options());
-  auto ws = torch::zeros({N * groups * 2}, x.options().dtype(torch::kFloat32));
+  auto ws = gn_sums(op, x, groups, stats);
   groupnorm_silu_nhwc_bf16(x.data_ptr(), y.data_ptr(), ws.data_ptr<float>(),
                            gamma.data_ptr<float>(), beta.data_ptr<float>(),
                            (int)N, (int)C, HW, (int)groups, (float)eps,
-                           do_silu ? 1 : 0, cur_stream());
+                           do_silu ? 1 : 0, stats.has_value() ? 1 : 0,
+                           cur_stream());
   return y;
 }
 
@@ -814,9 +843,16 @@ ConvDims check_conv(const char* op, const torch::Tensor& x,
 
 // addend [N, K] bf16 is added per (image, output channel) after the conv's
 // own bf16 rounding; it excludes a residual (no caller needs the pair).
-torch::Tensor conv3x3(torch::Tensor x, torch::Tensor wr, torch::Tensor bias,
-                      c10::optional<torch::Tensor> residual, int64_t K,
-                      bool upsample, c10::optional<torch::Tensor> addend) {
+//
+// gn_groups > 0 also takes, in the epilogue, the GroupNorm sums of the output
+// for a following norm of that many groups (K / gn_groups a multiple of 4):
+// the second result, [N, gn_groups, 2] f32 (sum, sumsq), is what
+// groupnorm_silu* and conv3x3_gn accept as `stats`.  The output itself is
+// that of the call without.
+std::vector<torch::Tensor> conv3x3_impl(
+    torch::Tensor x, torch::Tensor wr, torch::Tensor bias,
+    c10::optional<torch::Tensor> residual, int64_t K, bool upsample,
+    c10::optional<torch::Tensor> addend, int64_t gn_groups) {
   const ConvDims d = check_conv("conv3x3", x, wr, bias, residual, K, upsample);
   if (addend.has_value()) {
     TORCH_CHECK(!residual.has_value(),
@@ -830,20 +866,61 @@ torch::Tensor conv3x3(torch::Tensor x, torch::Tensor wr, torch::Tensor bias,
                 addend->sizes());
   }
   auto out = torch::empty({d.N, K, d.Ho, d.Wo}, x.options());
+  torch::Tensor part;
+  int npix = 0, nquads = 0;
+  if (gn_groups > 0) {
+    TORCH_CHECK(K % gn_groups == 0 && (K / gn_groups) % 4 == 0,
+                "conv3x3: statistics need gn_groups that divide K into a "
+                "multiple of 4 channels, got gn_groups=", gn_groups, " K=", K);
+    conv3x3_stats_dims(d.Ho, d.Wo, (int)K, &npix, &nquads);
+    TORCH_CHECK((int64_t)npix * (K / gn_groups / 4) < (1ll << 31) &&
+                    d.N * gn_groups < (1ll << 29),
+                "conv3x3: too large for the statistics kernels, got x ",
+                x.sizes(), " K=", K);
+    part = torch::empty({d.N, npix, nquads, 2},
+                        x.options().dtype(torch::kFloat32));
+  }
   conv3x3_bf16(x.data_ptr(), wr.data_ptr(), bias.data_ptr(),
                residual.has_value() ? residual->data_ptr() : nullptr,
                addend.has_value() ? addend->data_ptr() : nullptr,
-               out.data_ptr(), nullptr, nullptr, d.N, d.C, d.Ho, d.Wo, (int)K,
-               d.C16, d.Kpad, upsample ? 1 : 0, cur_stream());
-  return out;
+               out.data_ptr(), nullptr, nullptr,
+               gn_groups > 0 ? part.data_ptr<float>() : nullptr, d.N, d.C,
+               d.Ho, d.Wo, (int)K, d.C16, d.Kpad, upsample ? 1 : 0,
+               cur_stream());
+  if (gn_groups <= 0) return {out};
+  // every slot is written: no zero fill
+  auto sums = torch::empty({d.N, gn_groups, 2},
+                           x.options().dtype(torch::kFloat32));
+  gn_stats_finalize(part.data_ptr<float>(), sums.data_ptr<float>(), d.N,
+                    (int)gn_groups, (int)(K / gn_groups / 4), npix, nquads,
+                    cur_stream());
+  return {out, sums};
+}
+
+torch::Tensor conv3x3(torch::Tensor x, torch::Tensor wr, torch::Tensor bias,
+                      c10::optional<torch::Tensor> residual, int64_t K,
+                      bool upsample, c10::optional<torch::Tensor> addend) {
+  return conv3x3_impl(x, wr, bias, residual, K, upsample, addend, 0)[0];
+}
+
+std::vector<torch::Tensor> conv3x3_stats(
+    torch::Tensor x, torch::Tensor wr, torch::Tensor bias,
+    c10::optional<torch::Tensor> residual, int64_t K, bool upsample,
+    c10::optional<torch::Tensor> addend, int64_t gn_groups) {
+  TORCH_CHECK(gn_groups >= 1, "conv3x3: gn_groups must be at least 1, got ",
+              gn_groups);
+  return conv3x3_impl(x, wr, bias, residual, K, upsample, addend, gn_groups);
 }
 
 // GroupNorm+SiLU fused INTO the conv's staging read: one stats pass over x,
 // per-(n,c) coefficients, then the conv applies silu(x*sc+sh) while staging.
+// With `stats` (the sums of x from the conv that produced it) the stats pass
+// goes too: gn_coeff_kernel alone runs before the conv.
 torch::Tensor conv3x3_gn(torch::Tensor x, torch::Tensor wr, torch::Tensor bias,
                          c10::optional<torch::Tensor> residual, int64_t K,
                          bool upsample, torch::Tensor gamma,
-                         torch::Tensor beta, int64_t groups, double eps) {
+                         torch::Tensor beta, int64_t groups, double eps,
+                         c10::optional<torch::Tensor> stats) {
   const ConvDims d =
       check_conv("conv3x3_gn", x, wr, bias, residual, K, upsample);
   check_f32_vec(gamma, "gamma", d.C, "C");
@@ -854,19 +931,20 @@ torch::Tensor conv3x3_gn(torch::Tensor x, torch::Tensor wr, torch::Tensor bias,
   const int N = d.N, C16 = d.C16;
   long long HW = (long long)d.H * d.W;
   auto fopt = x.options().dtype(torch::kFloat32);
-  auto ws = torch::zeros({(long long)N * groups * 2}, fopt);
+  auto ws = gn_sums("conv3x3_gn", x, groups, stats);
   auto scale = torch::empty({(long long)N * C16}, fopt);
   auto shift = torch::empty({(long long)N * C16}, fopt);
   gn_conv_coeffs_bf16(x.data_ptr(), ws.data_ptr<float>(),
                       gamma.data_ptr<float>(), beta.data_ptr<float>(),
                       scale.data_ptr<float>(), shift.data_ptr<float>(), N, d.C,
-                      C16, HW, (int)groups, (float)eps, cur_stream());
+                      C16, HW, (int)groups, (float)eps,
+                      stats.has_value() ? 1 : 0, cur_stream());
   auto out = torch::empty({N, K, d.Ho, d.Wo}, x.options());
   conv3x3_bf16(x.data_ptr(), wr.data_ptr(), bias.data_ptr(),
                residual.has_value() ? residual->data_ptr() : nullptr,
                nullptr, out.data_ptr(), scale.data_ptr<float>(),
-               shift.data_ptr<float>(), N, d.C, d.Ho, d.Wo, (int)K, C16,
-               d.Kpad, upsample ? 1 : 0, cur_stream());
+               shift.data_ptr<float>(), nullptr, N, d.C, d.Ho, d.Wo, (int)K,
+               C16, d.Kpad, upsample ? 1 : 0, cur_stream());
   return out;
 }
 
@@ -1473,9 +1551,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("block_table"), py::arg("cu_q"), py::arg("seq_lens"),
         py::arg("block_size"), py::arg("scale"), py::arg("max_q_len"),
         py::arg("splits") = 0);
-  m.def("groupnorm_silu", &groupnorm_silu);
+  m.def("groupnorm_silu", &groupnorm_silu, py::arg("x"), py::arg("gamma"),
+        py::arg("beta"), py::arg("groups"), py::arg("eps"),
+        py::arg("do_silu"), py::arg("stats") = py::none());
   m.def("groupnorm_silu_nhwc", &groupnorm_silu_nhwc,
-        "GroupNorm(+SiLU) of NCHW x, written as [N, H*W, C]");
+        "GroupNorm(+SiLU) of NCHW x, written as [N, H*W, C]", py::arg("x"),
+        py::arg("gamma"), py::arg("beta"), py::arg("groups"), py::arg("eps"),
+        py::arg("do_silu"), py::arg("stats") = py::none());
   m.def("layernorm", &layernorm);
   m.def("add_layernorm", &add_layernorm,
         "(x + y, LayerNorm(x + y)) from one read of x and y");
@@ -1502,7 +1584,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         pybind11::arg("x"), pybind11::arg("wr"), pybind11::arg("bias"),
         pybind11::arg("residual"), pybind11::arg("K"),
         pybind11::arg("upsample"), pybind11::arg("addend") = pybind11::none());
-  m.def("conv3x3_gn", &conv3x3_gn, "GroupNorm+SiLU fused into the K3 conv");
+  m.def("conv3x3_stats", &conv3x3_stats,
+        "conv3x3 that also returns the GroupNorm sums of its output, "
+        "[N, gn_groups, 2], taken in the epilogue",
+        py::arg("x"), py::arg("wr"), py::arg("bias"), py::arg("residual"),
+        py::arg("K"), py::arg("upsample"), py::arg("addend"),
+        py::arg("gn_groups"));
+  m.def("conv3x3_gn", &conv3x3_gn, "GroupNorm+SiLU fused into the K3 conv",
+        py::arg("x"), py::arg("wr"), py::arg("bias"), py::arg("residual"),
+        py::arg("K"), py::arg("upsample"), py::arg("gamma"), py::arg("beta"),
+        py::arg("groups"), py::arg("eps"), py::arg("stats") = py::none());
   m.def("softmax_fwd", &softmax_fwd);
   m.def("moe_route", &moe_route,
         "MoE top-k routing: (weights fp32 [N,k], idx int32 [N,k])");

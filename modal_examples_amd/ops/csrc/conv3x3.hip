@@ -45,6 +45,21 @@
 //  - Offsets inside one image are 32-bit: the host checks C16*Hs*Ws and
 //    64*H*W below 2^31 elements (bindings.cpp check_conv).
 //
+//  - Optional GroupNorm statistics (`stats` non-null): the epilogue also sums
+//    the values AS STORED (the bf16 result widened back to f32) and their
+//    squares per aligned channel quad, for the GroupNorm that reads this
+//    tensor next.  A lane's 8 quads x (sum, sumsq) are summed over its rows
+//    in registers, halved across the 32 lanes of its half-wave (per
+//    k-fragment 4, 2, 1 values exchanged, then two butterflies: 18 cross-lane
+//    moves for 16 statistics), and the four
+//    waves meet in the LDS of the finished main loop.  The block writes its
+//    16 quad partials with plain stores to stats[n][pixel tile][quad][2]
+//    (32 consecutive floats);
+//    gn_stats_finalize_kernel (norms.hip) sums them per (n, group) in a fixed
+//    order.  No atomics: the statistics are deterministic.  Masked pixels
+//    and channels past K add nothing; the stored output is that of a call
+//    without statistics (same arithmetic, a separate epilogue instance).
+//
 // The kernel is stride-1/pad-1 only; stride-2 downsample convs (3 per UNet
 // fwd) stay on the library path.
 #include "common.h"
@@ -102,7 +117,8 @@ void conv3x3_kernel(
     const short* __restrict__ in, const short* __restrict__ wr,
     const float* __restrict__ bias, const short* __restrict__ res,
     const short* __restrict__ addend, short* __restrict__ out, const float* __restrict__ gn_scale,
-    const float* __restrict__ gn_shift, int C, int H, int W, int Hs, int Ws,
+    const float* __restrict__ gn_shift, float* __restrict__ stats, int C,
+    int H, int W, int Hs, int Ws,
     int K, int C16, int Kpad, int npix_x, int npix, int nk) {
   constexpr int CV_ROWS = CV_NW * RPW;
   constexpr int PATCH_R = CV_ROWS + 2;
@@ -114,6 +130,7 @@ void conv3x3_kernel(
   __shared__ alignas(16) short wlds[WLDS_ELEMS];
   __shared__ alignas(16) float bias_s[CV_BK];
   __shared__ alignas(16) float addend_s[CV_BK];
+  __shared__ unsigned long long stat_dst_s;
 
   const int tid = threadIdx.x;
   const int w = tid / WAVE;
@@ -149,6 +166,15 @@ void conv3x3_kernel(
     const int kc = min(k0 + tid, K - 1);
     bias_s[tid] = bias[kc];
     if (addend != nullptr) addend_s[tid] = bf2f(addend[(long long)n * K + kc]);
+  }
+
+  // statistics: where this block's 16 quad partials go (0: none asked for).
+  // Parked in LDS so that neither the pointer nor the tile counts stay in
+  // scalar registers across the main loop, which has none to spare.
+  if (tid == 0) {
+    const long long e = ((long long)n * npix + pix) * (nk * (CV_BK / 4)) +
+                        ktile * (CV_BK / 4);
+    stat_dst_s = stats != nullptr ? (unsigned long long)(stats + e * 2) : 0ull;
   }
 
   // ---- staging: slot s = (row, col, c-oct); thread gathers 8 strided
@@ -330,10 +356,12 @@ void conv3x3_kernel(
   // per-element condition.  Edge tiles clamp (y, x, k) for the residual
   // loads and mask the stores; interior tiles have no condition at all.
   // Offsets inside the block's (n, k0) slab of 64 planes are 32-bit.
-  auto epilogue = [&](auto res_c, auto add_c, auto edge_c) {
+  auto epilogue = [&](auto res_c, auto add_c, auto edge_c, auto stat_c,
+                      float* stat_dst) {
     constexpr bool RES = decltype(res_c)::value;
     constexpr bool ADD = decltype(add_c)::value;
     constexpr bool EDGE = decltype(edge_c)::value;
+    constexpr bool STAT = decltype(stat_c)::value;
     // lane coordinates rebuilt from an opaque copy of tid: kept live across
     // the main loop they cost registers the loop has not got
     int t = tid;
@@ -346,40 +374,116 @@ void conv3x3_kernel(
     char* outb = (char*)(out + slab);
     const int x = x0 + l31;
     const int kmax = K - 1 - k0;  // last valid k of this tile (EDGE)
-#pragma unroll
-    for (int rr = 0; rr < RPW; ++rr) {
+    // st[i], i = 4*{sum, sumsq} + q: the lane's quad sums of one k-fragment
+    // over its rows
+    float st[STAT ? 8 : 1];
+    // edge tiles: a 0/-1 mask ANDed onto the bits of a counted value, sign-bit
+    // arithmetic like the staging masks.  As a second use of the stores'
+    // condition every element's lane mask stays live in scalar registers.
+    // K is a multiple of 4 here, so a quad is below K as a whole.
+    const int kq = 4 * hi5 - kmax - 1;  // + the quad's mf*32 + 8*q: < 0 below K
+    // one (row, k-fragment) of the wave's tile: 16 values per lane
+    auto frag = [&](int rr, int mf) {
       const int y = y0 + w * RPW + rr;
       const bool pix_ok = !EDGE || (y < H && x < W);
       const unsigned po = EDGE ? (unsigned)min(y, H - 1) * W + min(x, W - 1)
                                : (unsigned)y * W + x;
+      int pmask = -1;  // STAT && EDGE: 0 for a pixel past H or W
+      if constexpr (STAT && EDGE)
+        pmask = (((y - H) >> 31) & ((x - W) >> 31));
+      unsigned rv[16];
+      if constexpr (RES) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+          const int kl = mf * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi5;
+          const unsigned ke = EDGE ? min(kl, kmax) : kl;
+          rv[r] = *(const unsigned short*)(resb + (po + ke * hw) * 2u);
+        }
+      }
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const f32x4 b4 = *(const f32x4*)&bias_s[mf * 32 + 8 * q + 4 * hi5];
+        f32x4 a4;
+        int qm = -1;  // STAT && EDGE: 0 for a quad past K or a pixel outside
+        if constexpr (STAT && EDGE)
+          qm = ((mf * 32 + 8 * q + kq) >> 31) & pmask;
+        if constexpr (ADD)
+          a4 = *(const f32x4*)&addend_s[mf * 32 + 8 * q + 4 * hi5];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int r = q * 4 + j;
+          const int kl = mf * 32 + j + 8 * q + 4 * hi5;
+          float v = acc[rr][mf][r] + b4[j];
+          if constexpr (RES) v += bf2f((short)rv[r]);
+          if constexpr (ADD) v = bf2f(f2bf(v)) + a4[j];
+          const short o = f2bf(v);
+          if (!EDGE || (pix_ok && kl <= kmax))
+            *(short*)(outb + (po + (unsigned)kl * hw) * 2u) = o;
+          if constexpr (STAT) {
+            float f = bf2f(o);
+            if constexpr (EDGE) f = __int_as_float(__float_as_int(f) & qm);
+            st[q] += f;
+            st[4 + q] = fmaf(f, f, st[4 + q]);
+          }
+        }
+        // one quad at a time: scheduled as a whole, the 64 rounded values
+        // and their widened copies are all live at once and spill
+        if constexpr (STAT) __builtin_amdgcn_sched_barrier(0);
+      }
+    };
+    if constexpr (!STAT) {
+#pragma unroll
+      for (int rr = 0; rr < RPW; ++rr)
+#pragma unroll
+        for (int mf = 0; mf < 2; ++mf) frag(rr, mf);
+    } else {
+      // k-fragment by k-fragment, so that 8 sums are live at a time and the
+      // first fragment's accumulators are dead during the second.  Halving
+      // exchange inside the half-wave: at lane bit b a lane keeps the upper
+      // half of its values if the bit is set, else the lower, and adds the
+      // partner's copy of that half; after bits 4..2 one value is left,
+      // st index (l31 >> 2), and bits 1, 0 are plain butterflies: 9 moves
+      // for a fragment's 8 statistics.
+      const bool b4 = l31 & 16, b3 = l31 & 8, b2 = l31 & 4;
+      float sred[2];
 #pragma unroll
       for (int mf = 0; mf < 2; ++mf) {
-        unsigned rv[16];
-        if constexpr (RES) {
 #pragma unroll
-          for (int r = 0; r < 16; ++r) {
-            const int kl = mf * 32 + (r & 3) + 8 * (r >> 2) + 4 * hi5;
-            const unsigned ke = EDGE ? min(kl, kmax) : kl;
-            rv[r] = *(const unsigned short*)(resb + (po + ke * hw) * 2u);
-          }
-        }
+        for (int i = 0; i < 8; ++i) st[i] = 0.f;
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-          const f32x4 b4 = *(const f32x4*)&bias_s[mf * 32 + 8 * q + 4 * hi5];
-          f32x4 a4;
-          if constexpr (ADD)
-            a4 = *(const f32x4*)&addend_s[mf * 32 + 8 * q + 4 * hi5];
+        for (int rr = 0; rr < RPW; ++rr) frag(rr, mf);
+        float s4[4], s2[2], s1;
 #pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            const int r = q * 4 + j;
-            const int kl = mf * 32 + j + 8 * q + 4 * hi5;
-            float v = acc[rr][mf][r] + b4[j];
-            if constexpr (RES) v += bf2f((short)rv[r]);
-            if constexpr (ADD) v = bf2f(f2bf(v)) + a4[j];
-            if (!EDGE || (pix_ok && kl <= kmax))
-              *(short*)(outb + (po + (unsigned)kl * hw) * 2u) = f2bf(v);
-          }
-        }
+        for (int i = 0; i < 4; ++i)
+          s4[i] = (b4 ? st[4 + i] : st[i]) +
+                  __shfl_xor(b4 ? st[i] : st[4 + i], 16, WAVE);
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+          s2[i] = (b3 ? s4[2 + i] : s4[i]) +
+                  __shfl_xor(b3 ? s4[i] : s4[2 + i], 8, WAVE);
+        s1 = (b2 ? s2[1] : s2[0]) + __shfl_xor(b2 ? s2[0] : s2[1], 4, WAVE);
+        s1 += __shfl_xor(s1, 2, WAVE);
+        s1 += __shfl_xor(s1, 1, WAVE);
+        sred[mf] = s1;
+      }
+      // the four waves meet in the patch's LDS: every wave has left the main
+      // loop once it is past this barrier
+      float* red = (float*)patch;  // [wave][hi5][mf][8]
+      __syncthreads();
+      if ((l31 & 3) == 0) {
+        red[((w * 2 + hi5) * 2 + 0) * 8 + (l31 >> 2)] = sred[0];
+        red[((w * 2 + hi5) * 2 + 1) * 8 + (l31 >> 2)] = sred[1];
+      }
+      __syncthreads();
+      if (t < 32) {
+        // thread = (quad of the tile, statistic); quad cq covers channels
+        // k0 + 4*cq .. +3 = mf*32 + 8*q + 4*hi5
+        const int cq = t >> 1, sq = t & 1;
+        const int i = (((cq & 1) * 2 + (cq >> 3)) * 8) + sq * 4 + ((cq >> 1) & 3);
+        float a = 0.f;
+#pragma unroll
+        for (int ww = 0; ww < CV_NW; ++ww) a += red[ww * 32 + i];
+        stat_dst[t] = a;  // t = 2 * cq + sq
       }
     }
   };
@@ -387,33 +491,55 @@ void conv3x3_kernel(
       y0 + CV_ROWS > H || x0 + CV_COLS > W || k0 + CV_BK > K;
   const std::true_type yes{};
   const std::false_type no{};
-  if (res != nullptr) {
-    if (edge) epilogue(yes, no, yes);
-    else epilogue(yes, no, no);
-  } else if (addend != nullptr) {
-    if (edge) epilogue(no, yes, yes);
-    else epilogue(no, yes, no);
-  } else {
-    if (edge) epilogue(no, no, yes);
-    else epilogue(no, no, no);
-  }
+  const unsigned long long sd = stat_dst_s;  // written before the loop
+  float* const stat_dst = (float*)(((unsigned long long)(unsigned)to_sgpr(
+                                        (int)(sd >> 32)) << 32) |
+                                   (unsigned)to_sgpr((int)sd));
+  auto dispatch = [&](auto stat_c) {
+    if (res != nullptr) {
+      if (edge) epilogue(yes, no, yes, stat_c, stat_dst);
+      else epilogue(yes, no, no, stat_c, stat_dst);
+    } else if (addend != nullptr) {
+      if (edge) epilogue(no, yes, yes, stat_c, stat_dst);
+      else epilogue(no, yes, no, stat_c, stat_dst);
+    } else {
+      if (edge) epilogue(no, no, yes, stat_c, stat_dst);
+      else epilogue(no, no, no, stat_c, stat_dst);
+    }
+  };
+  if (stat_dst != nullptr) dispatch(yes);
+  else dispatch(no);
 }
 
-extern "C" void conv3x3_bf16(const void* in, const void* wrepack,
-                             const void* bias, const void* residual,
-                             const void* addend, void* out,
-                             const float* gn_scale, const float* gn_shift,
-                             int N, int C, int H, int W, int K, int C16,
-                             int Kpad, int upsample, hipStream_t stream) {
-  // H/W are the OUTPUT dims; with upsample the source is H/2 x W/2.
-  const int Hs = upsample ? H / 2 : H;
-  const int Ws = upsample ? W / 2 : W;
+static int conv_rpw() {
   // rows-per-wave A/B (MODAL_AMD_CONV_RPW=4): doubles MFMA per staged
   // byte/A-read at 1 wave/SIMD occupancy.
   static const int rpw = [] {
     const char* e = getenv("MODAL_AMD_CONV_RPW");
     return (e && atoi(e) == 4) ? 4 : 2;
   }();
+  return rpw;
+}
+
+// The statistics workspace of an H x W x K output: [N][npix][nquads][2] f32.
+extern "C" void conv3x3_stats_dims(int H, int W, int K, int* npix,
+                                   int* nquads) {
+  const int rows = CV_NW * conv_rpw();
+  *npix = ((W + CV_COLS - 1) / CV_COLS) * ((H + rows - 1) / rows);
+  *nquads = ((K + CV_BK - 1) / CV_BK) * (CV_BK / 4);
+}
+
+extern "C" void conv3x3_bf16(const void* in, const void* wrepack,
+                             const void* bias, const void* residual,
+                             const void* addend, void* out,
+                             const float* gn_scale, const float* gn_shift,
+                             float* stats, int N, int C, int H, int W, int K,
+                             int C16,
+                             int Kpad, int upsample, hipStream_t stream) {
+  // H/W are the OUTPUT dims; with upsample the source is H/2 x W/2.
+  const int Hs = upsample ? H / 2 : H;
+  const int Ws = upsample ? W / 2 : W;
+  const int rpw = conv_rpw();
   const int rows = CV_NW * rpw;
   const int npix_x = (W + CV_COLS - 1) / CV_COLS;
   const int npix_y = (H + rows - 1) / rows;
@@ -427,7 +553,8 @@ extern "C" void conv3x3_bf16(const void* in, const void* wrepack,
                      stream, (const short*)in, (const short*)wrepack, \
                      (const float*)bias, (const short*)residual, \
                      (const short*)addend, (short*)out, \
-                     gn_scale, gn_shift, C, H, W, Hs, Ws, K, C16, Kpad, \
+                     gn_scale, gn_shift, stats, C, H, W, Hs, Ws, K, C16, \
+                     Kpad, \
                      npix_x, npix, nk)
   if (rpw == 4) {
     if (upsample) {

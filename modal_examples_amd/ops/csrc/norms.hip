@@ -209,16 +209,71 @@ static int gn_split(int N, int G, long long HW) {
   return split;
 }
 
+// The sums of a tensor that conv3x3_kernel has just written, from the quad
+// partials of its epilogue: part [N][npix][nquads][2] f32 (conv3x3.hip), one
+// (sum, sumsq) per (image, pixel tile, aligned channel quad); a group is cpg4
+// consecutive quads.  One block per (n, group) adds the group's npix * cpg4
+// entries in a fixed order - thread t takes entries t, t + 256, ..., then a
+// tree over the block - and writes both WS slots, so WS needs no zero fill
+// and the result does not depend on the order in which conv blocks finished.
+#ifdef __HIP_DEVICE_COMPILE__
+#define GN_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#else
+#define GN_NO_PK_F32  // the host pass does not know the feature
+#endif
+
+GN_NO_PK_F32 __global__ __launch_bounds__(256) void gn_stats_finalize_kernel(
+    const f32x2* __restrict__ part, float* __restrict__ WS, int G, int cpg4,
+    int npix, int nquads) {
+  __shared__ float red[2][256];
+  const int ng = blockIdx.x;
+  const int n = ng / G, g = ng % G;
+  const f32x2* p = part + (long long)n * npix * nquads + g * cpg4;
+  const int total = npix * cpg4;
+  float s = 0.f, ss = 0.f;
+  for (int e = threadIdx.x; e < total; e += 256) {
+    const int px = e / cpg4, qi = e - px * cpg4;
+    const f32x2 v = p[(long long)px * nquads + qi];
+    s += v[0];
+    ss += v[1];
+  }
+  red[0][threadIdx.x] = s;
+  red[1][threadIdx.x] = ss;
+  __syncthreads();
+  for (int h = 128; h > 0; h >>= 1) {
+    if ((int)threadIdx.x < h) {
+      red[0][threadIdx.x] += red[0][threadIdx.x + h];
+      red[1][threadIdx.x] += red[1][threadIdx.x + h];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x < 2) WS[ng * 2 + threadIdx.x] = red[threadIdx.x][0];
+}
+
+// npix * cpg4 < 2^31 (checked by the binding).
+extern "C" void gn_stats_finalize(const float* part, float* ws, int N, int G,
+                                  int cpg4, int npix, int nquads,
+                                  hipStream_t stream) {
+  if (N * G == 0) return;
+  hipLaunchKernelGGL(gn_stats_finalize_kernel, dim3(N * G), dim3(256), 0,
+                     stream, (const f32x2*)part, ws, G, cpg4, npix, nquads);
+}
+
+// have_sums (all three entries below): ws already holds the (sum, sumsq) of
+// x per (n, group) - from gn_stats_finalize - and the statistics pass over x
+// is skipped.  Otherwise ws must be zero on entry.
+
 // y: [N, HW, C].  HW < 2^31 (checked by the binding).
 extern "C" void groupnorm_silu_nhwc_bf16(const void* x, void* y, float* ws,
                                          const float* gamma, const float* beta,
                                          int N, int C, long long HW, int G,
-                                         float eps, int do_silu,
+                                         float eps, int do_silu, int have_sums,
                                          hipStream_t stream) {
   if (N == 0 || C == 0 || HW == 0) return;
   const int split = gn_split(N, G, HW);
-  hipLaunchKernelGGL(gn_partial_kernel, dim3(N * G * split), dim3(256), 0,
-                     stream, (const short*)x, ws, N, C, HW, G, split);
+  if (!have_sums)
+    hipLaunchKernelGGL(gn_partial_kernel, dim3(N * G * split), dim3(256), 0,
+                       stream, (const short*)x, ws, N, C, HW, G, split);
   dim3 grid((unsigned)((HW + TT - 1) / TT), (C + TT - 1) / TT, N);
   hipLaunchKernelGGL(gn_norm_nhwc_kernel, grid, dim3(256), 0, stream,
                      (const short*)x, (short*)y, ws, gamma, beta, C, (int)HW,
@@ -228,12 +283,13 @@ extern "C" void groupnorm_silu_nhwc_bf16(const void* x, void* y, float* ws,
 extern "C" void groupnorm_silu_bf16(const void* x, void* y, float* ws,
                                     const float* gamma, const float* beta,
                                     int N, int C, long long HW, int G,
-                                    float eps, int do_silu,
+                                    float eps, int do_silu, int have_sums,
                                     hipStream_t stream) {
   const int split = gn_split(N, G, HW);
   dim3 grid(N * G * split);
-  hipLaunchKernelGGL(gn_partial_kernel, grid, dim3(256), 0, stream,
-                     (const short*)x, ws, N, C, HW, G, split);
+  if (!have_sums)
+    hipLaunchKernelGGL(gn_partial_kernel, grid, dim3(256), 0, stream,
+                       (const short*)x, ws, N, C, HW, G, split);
   hipLaunchKernelGGL(gn_norm_kernel, grid, dim3(256), 0, stream,
                      (const short*)x, (short*)y, ws, gamma, beta, N, C, HW, G,
                      eps, do_silu, split);
@@ -455,10 +511,11 @@ extern "C" void gn_conv_coeffs_bf16(const void* x, float* ws,
                                     const float* gamma, const float* beta,
                                     float* scale, float* shift, int N, int C,
                                     int Cpad, long long HW, int G, float eps,
-                                    hipStream_t stream) {
+                                    int have_sums, hipStream_t stream) {
   const int split = gn_split(N, G, HW);
-  hipLaunchKernelGGL(gn_partial_kernel, dim3(N * G * split), dim3(256), 0,
-                     stream, (const short*)x, ws, N, C, HW, G, split);
+  if (!have_sums)
+    hipLaunchKernelGGL(gn_partial_kernel, dim3(N * G * split), dim3(256), 0,
+                       stream, (const short*)x, ws, N, C, HW, G, split);
   hipLaunchKernelGGL(gn_coeff_kernel, dim3((N * Cpad + 255) / 256), dim3(256),
                      0, stream, ws, gamma, beta, scale, shift, N, C, Cpad, HW,
                      G, eps);

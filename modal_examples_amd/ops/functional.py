@@ -256,14 +256,21 @@ def paged_decode_packed(q, k_cache, v_cache, block_table, cu_q, seq_lens,
 
 
 def groupnorm_silu(x, gamma, beta, groups: int = 32, eps: float = 1e-5,
-                   do_silu: bool = True, out_nhwc: bool = False):
+                   do_silu: bool = True, out_nhwc: bool = False, stats=None):
     """GroupNorm(+SiLU) of x [N,C,H,W].  out_nhwc=True returns the result as
     [N, H*W, C] — `groupnorm_silu(x).permute(0, 2, 3, 1).reshape(N, H*W, C)`
     — which the kernel writes directly (same statistics pass, an apply kernel
     that transposes its tile in LDS), so the sequence-major sections of the
-    UNet/VAE take it without a transposing copy."""
+    UNet/VAE take it without a transposing copy.
+
+    stats: the second result of `conv3x3(..., gn_groups=groups)` when that
+    call produced x; the statistics pass over x is then skipped.  None (which
+    is what conv3x3 returns when it took none) computes them here."""
     ext = _ext_for(x, gamma, beta)
     if ext is None:
+        if stats is not None:
+            raise ValueError("groupnorm_silu: stats come from the conv3x3 "
+                             "kernel and x is not on its path")
         y = ref.groupnorm_silu_ref(x, gamma, beta, groups, eps, do_silu)
         if out_nhwc:
             N, C, H, W = x.shape
@@ -271,7 +278,7 @@ def groupnorm_silu(x, gamma, beta, groups: int = 32, eps: float = 1e-5,
         return y
     fn = ext.groupnorm_silu_nhwc if out_nhwc else ext.groupnorm_silu
     return fn(x.contiguous(), gamma.float().contiguous(),
-              beta.float().contiguous(), groups, eps, do_silu)
+              beta.float().contiguous(), groups, eps, do_silu, stats)
 
 
 def layernorm(x, gamma, beta, eps: float = 1e-5):
@@ -421,16 +428,38 @@ def repack_conv3x3_weight(weight: torch.Tensor) -> torch.Tensor:
 
 
 def conv3x3(x, wr, bias, K: int, residual=None, raw_weight=None,
-            upsample: bool = False, addend=None):
+            upsample: bool = False, addend=None, gn_groups=None):
     """3x3 stride-1 pad-1 conv (K3). x [N,C,H,W] bf16; wr from
     repack_conv3x3_weight; bias fp32 [K]; optional fused residual add;
     upsample=True fuses a nearest-2x upsample of x into the conv read.
     addend [N,K] (x's dtype) is added per (image, output channel) to the
     rounded conv output — `conv3x3(x, ...) + addend[:, :, None, None]` in the
     kernel's epilogue; it cannot be combined with residual.
-    raw_weight [K,C,3,3] drives the CPU/autograd reference path."""
+    raw_weight [K,C,3,3] drives the CPU/autograd reference path.
+
+    gn_groups=G returns (out, stats) for a GroupNorm of G groups that reads
+    `out` next: the kernel's epilogue takes the sums of the values it stores,
+    and `groupnorm_silu(out, ..., groups=G, stats=stats)` or
+    `conv3x3_gn(out, ..., stats=stats)` skips its statistics pass.  `out` is
+    that of the call without.  stats is None where the kernel takes none (K/G
+    no multiple of 4, or off the kernel path); the consumer then computes
+    them itself, so callers pass it on unexamined."""
     if addend is not None and residual is not None:
         raise ValueError("conv3x3: addend and residual cannot be combined")
+    if gn_groups is not None:
+        if gn_groups < 1 or K % gn_groups:
+            raise ValueError(f"conv3x3: gn_groups must be at least 1 and "
+                             f"divide K, got gn_groups={gn_groups} K={K}")
+        ext = _ext_for(x, raw_weight if raw_weight is not None else x, addend)
+        if ext is None or (K // gn_groups) % 4:
+            return conv3x3(x, wr, bias, K, residual, raw_weight, upsample,
+                           addend), None
+        out, stats = ext.conv3x3_stats(
+            x.contiguous(), wr, bias,
+            residual.contiguous() if residual is not None else None, K,
+            upsample, addend.contiguous() if addend is not None else None,
+            gn_groups)
+        return out, stats
     ext = _ext_for(x, raw_weight if raw_weight is not None else x, addend)
     if ext is not None and addend is not None:
         return ext.conv3x3(x.contiguous(), wr, bias, None, K, upsample,
@@ -457,13 +486,17 @@ def conv3x3(x, wr, bias, K: int, residual=None, raw_weight=None,
 
 def conv3x3_gn(x, wr, bias, K: int, gamma, beta, groups: int = 32,
                eps: float = 1e-5, residual=None, raw_weight=None,
-               upsample: bool = False):
+               upsample: bool = False, stats=None):
     """GroupNorm+SiLU fused into the K3 conv's staging read: one stats pass
     over x + the conv — the gn_norm write/read pass over the full tensor
-    disappears."""
+    disappears.  With stats (see conv3x3's gn_groups)
+    the stats pass goes as well."""
     ext = _ext_for(x, raw_weight if raw_weight is not None else x)
     if ext is None:
         assert raw_weight is not None
+        if stats is not None:
+            raise ValueError("conv3x3_gn: stats come from the conv3x3 kernel "
+                             "and x is not on its path")
         h = torch.nn.functional.group_norm(x.float(), groups, gamma.float(),
                                            beta.float(), eps)
         h = torch.nn.functional.silu(h)
@@ -478,7 +511,7 @@ def conv3x3_gn(x, wr, bias, K: int, gamma, beta, groups: int = 32,
     return ext.conv3x3_gn(x.contiguous(), wr, bias,
                           residual.contiguous() if residual is not None else None,
                           K, upsample, gamma.float().contiguous(),
-                          beta.float().contiguous(), groups, eps)
+                          beta.float().contiguous(), groups, eps, stats)
 
 
 def adamw_step(p, g, m, v, lr, beta1=0.9, beta2=0.999, eps=1e-8, wd=0.01, step=1):

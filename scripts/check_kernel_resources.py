@@ -40,11 +40,24 @@ OCCUPANCY_FLOORS = {
     "paged_decode_packed_kernelILi64E": 3,
     "paged_decode_packed_kernelILi128E": 2,
     # conv3x3_kernel<UP, GN, RPW=2>: 64 accumulators + a chunk of staged
-    # loads in flight must stay within 168 registers
+    # loads in flight must stay within 168 registers; the epilogue's
+    # GroupNorm statistics (8 sums per k-fragment) live after the loop and
+    # must not raise that
     "conv3x3_kernelILb0ELb0ELi2E": 3,
     "conv3x3_kernelILb1ELb0ELi2E": 3,
     "conv3x3_kernelILb0ELb1ELi2E": 3,
     "conv3x3_kernelILb1ELb1ELi2E": 3,
+    # conv3x3_kernel<UP, GN, RPW=4>: 128 accumulators, one wave per SIMD
+    "conv3x3_kernelILb0ELb0ELi4E": 1,
+    "conv3x3_kernelILb1ELb0ELi4E": 1,
+    "conv3x3_kernelILb0ELb1ELi4E": 1,
+    "conv3x3_kernelILb1ELb1ELi4E": 1,
+    # one block per (image, group) sums the conv epilogue's quad partials
+    "gn_stats_finalize_kernel": 8,
+    "gn_partial_kernel": 8,
+    "gn_norm_kernel": 8,
+    "gn_norm_nhwc_kernel": 8,
+    "gn_coeff_kernel": 8,
     "decode_merge_kernel": 4,
     # moe_gemm_kernel<UP, NF>: two register sets of NF-step chunks in flight
     # beside 32 accumulators; one wave per SIMD already covers the decode
