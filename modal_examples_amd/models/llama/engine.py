@@ -32,7 +32,8 @@ from .lora import LoraBank
 from .model import (EXPERT_DTYPES, WEIGHT_DTYPES, LlamaConfig, LlamaModel,
                     MoEFFN, quantize_llama_, quantize_llama_expert_state,
                     quantize_llama_experts_, quantize_llama_fp8_,
-                    quantize_llama_fp8_state, quantize_llama_state)
+                    quantize_llama_fp8_state, quantize_llama_mxfp4_,
+                    quantize_llama_mxfp4_state, quantize_llama_state)
 
 BLOCK = 16
 
@@ -145,7 +146,7 @@ class LlamaEngine:
         decodes eagerly whatever use_graph says; "fused" captures and
         replays like a dense model.  Every other lane calls the same FFN.
 
-        weight_dtype: "bf16" (default), "int4" or "fp8".  "int4" holds qkv,
+        weight_dtype: "bf16" (default), "int4", "fp8" or "mxfp4".  "int4" holds qkv,
         o_proj, gate_up and down of every block as 4-bit weights with one bf16 scale
         per 128 inputs (ops.quantize_w4; model.QuantLinear): 0.52 bytes per
         weight instead of 2.  Decode batches run them on the
@@ -166,7 +167,12 @@ class LlamaEngine:
         inside the decode graph, larger ones dequantize into a scratch
         weight.  Everything else said for "int4" (what stays in `dtype`,
         quantization before the KV pool is sized, init_weights=False, tp,
-        MoE configs) holds for it unchanged.
+        MoE configs) holds for it unchanged.  "mxfp4" holds them as OCP MX
+        fp4: two e2m1 codes a byte with one E8M0 scale byte per 32 inputs
+        (ops.quantize_mxfp4; model.Mxfp4Linear), 0.53 bytes per weight,
+        activations quantized per token to e4m3 as for "fp8"; batches up to
+        Mxfp4Linear.M_KERNEL rows run on the csrc/linear_mxfp4.hip kernel
+        inside the decode graph, and everything else is as for "fp8".
 
         expert_dtype: "bf16" or "int4"; None keeps cfg.expert_dtype.  "int4"
         holds the experts of every MoE block as 4-bit weights with one bf16
@@ -287,6 +293,8 @@ class LlamaEngine:
                     quantize_llama_(self.model)
                 elif weight_dtype == "fp8":
                     quantize_llama_fp8_(self.model)
+                elif weight_dtype == "mxfp4":
+                    quantize_llama_mxfp4_(self.model)
                 else:
                     quantize_llama_experts_(self.model)
                 if self.device.type == "cuda":
@@ -375,8 +383,8 @@ class LlamaEngine:
         reference role: sglang_snapshot.py:176-218 warm/sleep/wake).  An
         int4 engine writes its packed `qweight` / `scales` tensors, an
         int4-expert engine its `gate_up_q` / `gate_up_s` / `down_q` /
-        `down_s` buffers, an fp8 engine its `qweight` / `wscale` tensors
-        (which `from_safetensors` does not read back yet)."""
+        `down_s` buffers, an fp8 or mxfp4 engine its `qweight` / `wscale`
+        tensors (which `from_safetensors` does not read back yet)."""
         from ...gpu import fastload
 
         return fastload.save_file(dict(self.model.state_dict()), path)
@@ -395,8 +403,8 @@ class LlamaEngine:
         holds; asking for "bf16" raises, and so does tp.world > 1, whose
         shards would cut through packed words).  A bf16 file with
         weight_dtype="int4" is sharded first, if tp is set, and then
-        quantized on the device, and so it is with weight_dtype="fp8" (files
-        that already hold fp8 weights are refused).  The same holds for
+        quantized on the device, and so it is with weight_dtype="fp8" and
+        "mxfp4" (files that already hold fp8 or mxfp4 weights are refused).  The same holds for
         expert_dtype: a file
         with `.gate_up_q` keys defaults it to "int4" and refuses "bf16", and
         a bf16 file with expert_dtype="int4" is quantized on the device after
@@ -406,10 +414,13 @@ class LlamaEngine:
         from ...gpu import fastload
 
         header, _, _ = fastload._parse(path)
-        if any(k.endswith(".wscale") for k in header):
-            raise ValueError(f"{path} holds fp8 weights; loading them is not "
-                             f"supported: boot the bf16 checkpoint with "
-                             f"weight_dtype='fp8' instead")
+        wscale = [m for k, m in header.items() if k.endswith(".wscale")]
+        if wscale:
+            # fp8 scales are fp32 [N], mxfp4 scales uint8 [N, K/32]
+            kind = "mxfp4" if len(wscale[0]["shape"]) == 2 else "fp8"
+            raise ValueError(f"{path} holds {kind} weights; loading them is "
+                             f"not supported: boot the bf16 checkpoint with "
+                             f"weight_dtype={kind!r} instead")
         packed = any(k.endswith(".qweight") for k in header)
         kw.setdefault("weight_dtype", "int4" if packed else "bf16")
         if packed and kw["weight_dtype"] != "int4":
@@ -454,6 +465,8 @@ class LlamaEngine:
             sd = quantize_llama_state(sd)
         if eng.weight_dtype == "fp8":
             sd = quantize_llama_fp8_state(sd)
+        if eng.weight_dtype == "mxfp4":
+            sd = quantize_llama_mxfp4_state(sd)
         if eng.expert_dtype == "int4" and not packed_experts:
             sd = quantize_llama_expert_state(sd)
         eng.model.load_state_dict(sd, assign=True)

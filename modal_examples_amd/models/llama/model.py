@@ -9,7 +9,8 @@ MI355X mapping:
   K6 decode   → gfx950 paged decode kernel over the paged KV cache
   RMSNorm / RoPE / SwiGLU → fused gfx950 kernels
   QKV and gate_up projections → single fused GEMMs (hipBLASLt), or the
-  int4 / fp8 kernels under weight_dtype (QuantLinear, Fp8Linear)
+  int4 / fp8 / mxfp4 kernels under weight_dtype (QuantLinear, Fp8Linear,
+  Mxfp4Linear)
 """
 from __future__ import annotations
 
@@ -57,7 +58,7 @@ class LlamaConfig:
                            rope_base=10000.0, max_seq=512, n_experts=4)
 
 
-WEIGHT_DTYPES = ("bf16", "int4", "fp8")
+WEIGHT_DTYPES = ("bf16", "int4", "fp8", "mxfp4")
 EXPERT_DTYPES = ("bf16", "int4")
 
 
@@ -205,6 +206,69 @@ class Fp8Linear(nn.Module):
                 f"out_features={self.out_features}, fp8 e4m3 per-channel")
 
 
+class Mxfp4Linear(nn.Module):
+    """Bias-free linear layer over MXFP4 weights (ops.quantize_mxfp4):
+    buffers `qweight` uint8 [out, in/2] (two e2m1 codes a byte) and `wscale`
+    uint8 [out, in/32] (E8M0 block scales), activations quantized per row to
+    e4m3 at run time.  Both buffers are integers, so `.to(dtype)` leaves
+    them alone.
+
+    Two lanes, as Fp8Linear.  Up to M_KERNEL rows the forward is
+    ops.linear_mxfp4: on the GPU the row-quantization kernel and the
+    block-scaled fp4 MFMA GEMM of csrc/linear_mxfp4.hip.  Above that the
+    weight is dequantized (exactly: w_hat has two mantissa bits) into a
+    scratch tensor of the activation dtype and goes through the ordinary
+    GEMM on the unquantized activations, so the two lanes differ by the
+    activation quantization.  On the CPU, in fp32 or under autograd, the
+    kernel lane is the reference composition."""
+
+    # rows up to which the kernel lane is taken.  Measured
+    # (profiles/linear_mxfp4.txt, first table, "mxfp4" against "mxfp4deq"):
+    # the kernel lane beats the dequantize lane on all four Llama-3-8B
+    # projections at every measured row count, at 2048 rows still by 246 /
+    # 991, 184 / 685, 856 / 4742 and 452 / 2418 us (the dequantization is
+    # several torch passes over the weight).  2048 is the largest count
+    # measured, so the switch stays there.
+    M_KERNEL = 2048
+
+    def __init__(self, in_features: int, out_features: int, device=None):
+        super().__init__()
+        if in_features % 128 != 0 or in_features < 128:
+            raise ValueError(f"Mxfp4Linear: in_features={in_features} must "
+                             f"be a multiple of 128")
+        if out_features % 64 != 0 or out_features < 64:
+            raise ValueError(f"Mxfp4Linear: out_features={out_features} "
+                             f"must be a multiple of 64")
+        self.in_features, self.out_features = in_features, out_features
+        self.register_buffer("qweight", torch.zeros(
+            out_features, in_features // 2, dtype=torch.uint8, device=device))
+        self.register_buffer("wscale", torch.full(
+            (out_features, in_features // 32), 127, dtype=torch.uint8,
+            device=device))
+
+    @classmethod
+    def from_linear(cls, lin: nn.Linear) -> "Mxfp4Linear":
+        if lin.bias is not None:
+            raise ValueError("Mxfp4Linear has no bias")
+        w = lin.weight.detach()
+        if w.dtype not in (torch.bfloat16, torch.float32):
+            w = w.float()
+        m = cls(lin.in_features, lin.out_features, device="meta")
+        m.qweight, m.wscale = OF.quantize_mxfp4(w.contiguous())
+        return m
+
+    def forward(self, x):
+        rows = x.numel() // self.in_features
+        if rows <= self.M_KERNEL:
+            return OF.linear_mxfp4(x, self.qweight, self.wscale)
+        w = OF.dequantize_mxfp4(self.qweight, self.wscale).to(x.dtype)
+        return nn.functional.linear(x, w)
+
+    def extra_repr(self):
+        return (f"in_features={self.in_features}, "
+                f"out_features={self.out_features}, mxfp4 e2m1 b32")
+
+
 QUANT_PROJECTIONS = ("qkv", "o_proj", "gate_up", "down")
 
 
@@ -274,6 +338,38 @@ def quantize_llama_fp8_state(state: dict) -> dict:
     return out
 
 
+def quantize_llama_mxfp4_(model: "LlamaModel") -> "LlamaModel":
+    """`quantize_llama_` for MXFP4: the four block projections become
+    Mxfp4Linear modules, one projection at a time."""
+    for blk in model.blocks:
+        if blk.moe is not None:
+            raise ValueError("mxfp4 weights do not cover MoE experts")
+        for name in QUANT_PROJECTIONS:
+            lin = getattr(blk, name)
+            if isinstance(lin, nn.Linear):
+                setattr(blk, name, Mxfp4Linear.from_linear(lin))
+    model.weight_dtype = "mxfp4"
+    return model
+
+
+def quantize_llama_mxfp4_state(state: dict) -> dict:
+    """`quantize_llama_state` for MXFP4: the four block projections replaced
+    by their uint8 `qweight` / `wscale` pair."""
+    out = {}
+    for k, v in state.items():
+        parts = k.split(".")
+        if (len(parts) == 4 and parts[0] == "blocks"
+                and parts[2] in QUANT_PROJECTIONS and parts[3] == "weight"):
+            if v.dtype not in (torch.bfloat16, torch.float32):
+                v = v.float()
+            q, s = OF.quantize_mxfp4(v.contiguous())
+            out[k[:-len("weight")] + "qweight"] = q
+            out[k[:-len("weight")] + "wscale"] = s
+        else:
+            out[k] = v
+    return out
+
+
 def quantize_llama_experts_(model: "LlamaModel") -> "LlamaModel":
     """Quantize the experts of every MoE block in place
     (MoEFFN.quantize_experts_), one matrix at a time so the bf16 copy of each
@@ -323,13 +419,14 @@ class LlamaBlock(nn.Module):
         if weight_dtype not in WEIGHT_DTYPES:
             raise ValueError(f"weight_dtype must be one of {WEIGHT_DTYPES}, "
                              f"got {weight_dtype!r}")
-        if weight_dtype in ("int4", "fp8"):
+        if weight_dtype != "bf16":
             # built with buffers of the right shape (meta-device boot);
             # a shard whose K is no multiple of 128 raises here
             if cfg.n_experts > 0:
                 raise ValueError(f"weight_dtype={weight_dtype!r} does not "
                                  f"cover MoE experts")
-            quant = QuantLinear if weight_dtype == "int4" else Fp8Linear
+            quant = {"int4": QuantLinear, "fp8": Fp8Linear,
+                     "mxfp4": Mxfp4Linear}[weight_dtype]
 
             def linear(i, o, bias=False):
                 return quant(i, o)
@@ -394,7 +491,8 @@ class LlamaModel(nn.Module):
         block as QuantLinear modules with empty buffers (for loading a
         quantized state); `quantize_llama_` converts an initialised bf16
         model in place.  weight_dtype="fp8" does the same with Fp8Linear
-        modules and `quantize_llama_fp8_`."""
+        modules and `quantize_llama_fp8_`, weight_dtype="mxfp4" with
+        Mxfp4Linear modules and `quantize_llama_mxfp4_`."""
         super().__init__()
         self.cfg = cfg
         self.weight_dtype = weight_dtype

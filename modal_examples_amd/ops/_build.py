@@ -34,6 +34,7 @@ HIP_SOURCES = [
     "linear_w4.hip",
     "lora.hip",
     "linear_fp8.hip",
+    "linear_mxfp4.hip",
 ]
 
 # Per-source compiler flags beyond `common`; scripts/check_kernel_resources.py
@@ -54,6 +55,10 @@ EXTRA_FLAGS = {
     # divisions must stay correctly rounded (csrc/linear_fp8.hip)
     "linear_fp8.hip": ["-Xclang", "-target-feature", "-Xclang",
                        "-packed-fp32-ops"],
+    # the same flags as the fp8 GEMM it shares a skeleton with, and likewise
+    # no fast-math flag
+    "linear_mxfp4.hip": ["-Xclang", "-target-feature", "-Xclang",
+                         "-packed-fp32-ops"],
 }
 
 

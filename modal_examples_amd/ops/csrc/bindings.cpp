@@ -115,6 +115,12 @@ int fp8_quant_rows_bf16(const void*, void*, float*, long long, int,
 int linear_fp8_bf16(const void*, const float*, const void*, const float*,
                     float*, void*, long long, int, int, int, int,
                     hipStream_t);
+// linear_mxfp4_plan / linear_mxfp4_bf16: as the fp8 pair, with u8 [N,K/2]
+// weights and u8 [N,K/32] E8M0 block scales
+int linear_mxfp4_plan(long long, int, int, int);
+int linear_mxfp4_bf16(const void*, const float*, const void*, const void*,
+                      float*, void*, long long, int, int, int, int,
+                      hipStream_t);
 // the LoRA launchers return 0 once launched, non-zero (nothing launched)
 // for a shape they do not support; lora_plan: the K-slice count of the
 // shrink GEMM (= planes of the workspace), 0 for an unsupported K
@@ -1260,6 +1266,77 @@ int64_t linear_fp8_splits(int64_t M, int64_t N, int64_t K, int64_t splits) {
   return linear_fp8_plan(M, (int)N, (int)K, (int)splits);
 }
 
+// ------------------------------------------------------------- MXFP4 W4A8
+// Format: linear_mxfp4.hip.  Supported: M >= 1, N a multiple of 64, K a
+// multiple of 128; every check raises before anything is launched.
+
+// xq fp8 [M,K], xscale fp32 [M], qweight uint8 [N,K/2], wscale uint8
+// [N,K/32].  splits / mtiles as linear_fp8 (tests and benchmarks only).
+// Returns [M,N] bf16.
+torch::Tensor linear_mxfp4(torch::Tensor xq, torch::Tensor xscale,
+                           torch::Tensor qweight, torch::Tensor wscale,
+                           int64_t splits, int64_t mtiles) {
+  TORCH_CHECK(xq.is_cuda() && xq.is_contiguous() &&
+                  xq.scalar_type() == torch::kFloat8_e4m3fn,
+              "linear_mxfp4: xq must be float8_e4m3fn, contiguous, on GPU");
+  TORCH_CHECK(xscale.is_cuda() && xscale.is_contiguous() &&
+                  xscale.scalar_type() == torch::kFloat32,
+              "linear_mxfp4: xscale must be fp32, contiguous, on GPU");
+  for (const auto* t : {&qweight, &wscale})
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
+                    t->scalar_type() == torch::kUInt8,
+                "linear_mxfp4: qweight and wscale must be uint8, contiguous, "
+                "on GPU");
+  TORCH_CHECK(xq.dim() == 2 && qweight.dim() == 2 && xscale.dim() == 1 &&
+                  wscale.dim() == 2,
+              "linear_mxfp4: xq must be [M,K], xscale [M], qweight [N,K/2], "
+              "wscale [N,K/32]");
+  const int64_t M = xq.size(0), K = xq.size(1), N = qweight.size(0);
+  TORCH_CHECK(M >= 1, "linear_mxfp4: xq has no rows");
+  TORCH_CHECK(K >= 128 && K % 128 == 0, "linear_mxfp4: K=", K,
+              " (must be a multiple of 128)");
+  TORCH_CHECK(N >= 64 && N % 64 == 0, "linear_mxfp4: N=", N,
+              " (must be a multiple of 64)");
+  TORCH_CHECK(qweight.size(1) == K / 2 && xscale.size(0) == M &&
+                  wscale.size(0) == N && wscale.size(1) == K / 32,
+              "linear_mxfp4: qweight ", qweight.sizes(), " / xscale ",
+              xscale.sizes(), " / wscale ", wscale.sizes(),
+              " do not match M=", M, " N=", N, " K=", K);
+  TORCH_CHECK(qweight.device() == xq.device() &&
+                  xscale.device() == xq.device() &&
+                  wscale.device() == xq.device(),
+              "linear_mxfp4: all tensors must be on xq's device");
+  TORCH_CHECK(M < (1ll << 31) && N < (1ll << 31) && K < (1ll << 31) &&
+                  splits >= 0 && splits < (1ll << 31) && mtiles >= 0 &&
+                  mtiles <= 2,
+              "linear_mxfp4: size out of range");
+  // the kernels read 16 B fragments and 2 B scale pairs
+  if ((uintptr_t)xq.data_ptr() % 16) xq = xq.clone();
+  if ((uintptr_t)qweight.data_ptr() % 16) qweight = qweight.clone();
+  if ((uintptr_t)wscale.data_ptr() % 4) wscale = wscale.clone();
+  const int S = linear_mxfp4_plan(M, (int)N, (int)K, (int)splits);
+  TORCH_CHECK(S >= 1, "linear_mxfp4: shape not supported by the kernel (M=",
+              M, " N=", N, " K=", K, " splits=", splits, ")");
+  auto out = torch::empty({M, N}, xq.options().dtype(torch::kBFloat16));
+  torch::Tensor ws;
+  if (S > 1) ws = torch::empty({S, M, N}, xscale.options());
+  int rc = linear_mxfp4_bf16(xq.data_ptr(), xscale.data_ptr<float>(),
+                             qweight.data_ptr(), wscale.data_ptr(),
+                             S > 1 ? ws.data_ptr<float>() : nullptr,
+                             out.data_ptr(), M, (int)N, (int)K, (int)splits,
+                             (int)mtiles, cur_stream());
+  TORCH_CHECK(rc == 0, "linear_mxfp4: shape not supported by the kernel (M=",
+              M, " N=", N, " K=", K, " splits=", splits, ")");
+  return out;
+}
+
+int64_t linear_mxfp4_splits(int64_t M, int64_t N, int64_t K, int64_t splits) {
+  TORCH_CHECK(M < (1ll << 31) && N < (1ll << 31) && K < (1ll << 31) &&
+                  splits >= 0 && splits < (1ll << 31),
+              "linear_mxfp4: size out of range");
+  return linear_mxfp4_plan(M, (int)N, (int)K, (int)splits);
+}
+
 // ---------------------------------------------------------------- multi-LoRA
 // Supported: S <= 32 adapters, R in {16, 32, 64}, K a multiple of 64, O a
 // multiple of 128, any N.  Every check raises before anything is launched;
@@ -1621,6 +1698,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("wscale"), py::arg("splits") = 0, py::arg("mtiles") = 0);
   m.def("linear_fp8_splits", &linear_fp8_splits,
         "K slices linear_fp8 uses for (M, N, K); 0 = unsupported shape",
+        py::arg("M"), py::arg("N"), py::arg("K"), py::arg("splits") = 0);
+  m.def("linear_mxfp4", &linear_mxfp4,
+        "MXFP4 weight linear: block-scaled fp4 MFMA on the loaded bytes",
+        py::arg("xq"), py::arg("xscale"), py::arg("qweight"),
+        py::arg("wscale"), py::arg("splits") = 0, py::arg("mtiles") = 0);
+  m.def("linear_mxfp4_splits", &linear_mxfp4_splits,
+        "K slices linear_mxfp4 uses for (M, N, K); 0 = unsupported shape",
         py::arg("M"), py::arg("N"), py::arg("K"), py::arg("splits") = 0);
   m.def("lora_schedule", &lora_schedule,
         "multi-LoRA row schedule: rows grouped by adapter into 32-row tiles",

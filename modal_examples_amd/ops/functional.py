@@ -1140,3 +1140,106 @@ def linear_fp8(x, qweight, wscale):
     xq, xs = ext.quantize_rows_fp8(x.reshape(-1, K).contiguous())
     y = ext.linear_fp8(xq, xs, qweight, wscale)
     return y.view(*x.shape[:-1], N)
+
+
+# ---- MXFP4 weight linear.  Supported shapes (csrc/linear_mxfp4.hip): K a
+# multiple of 128, N a multiple of 64, any number of rows >= 1, contiguous
+# weights.  As for int4 and fp8, the checks run on every device, before the
+# dispatch.
+
+def _check_mxfp4_weight(qweight, wscale):
+    """Returns (N, K) of a quantized weight."""
+    if qweight.dtype is not torch.uint8:
+        raise TypeError(f"qweight must be uint8, got {qweight.dtype}")
+    if wscale.dtype is not torch.uint8:
+        raise TypeError(f"wscale must be uint8, got {wscale.dtype}")
+    if qweight.dim() != 2 or wscale.dim() != 2:
+        raise ValueError(f"qweight must be [N, K/2] and wscale [N, K/32], "
+                         f"got {tuple(qweight.shape)}, {tuple(wscale.shape)}")
+    N, K = qweight.shape[0], qweight.shape[1] * 2
+    if K < 128 or K % 128 != 0:
+        raise ValueError(f"qweight has K={K} (must be a multiple of 128)")
+    if N < 64 or N % 64 != 0:
+        raise ValueError(f"qweight has N={N} (must be a multiple of 64)")
+    if tuple(wscale.shape) != (N, K // 32):
+        raise ValueError(f"wscale must be [N={N}, K/32={K // 32}], got "
+                         f"{tuple(wscale.shape)}")
+    if wscale.device != qweight.device:
+        raise ValueError(f"wscale is on {wscale.device}, qweight on "
+                         f"{qweight.device}")
+    for name, t in (("qweight", qweight), ("wscale", wscale)):
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+    return N, K
+
+
+def quantize_mxfp4(weight):
+    """weight [N, K] (bf16 or fp32) -> (qweight uint8 [N, K/2], wscale uint8
+    [N, K/32]): OCP MX v1.0 fp4, done offline in torch ops.
+
+    Per block of 32 along K: e = floor(log2(absmax)) - 2, wscale = e + 127
+    (E8M0), codes = rne_e2m1(w / 2^e) saturating at +-6; an all-zero block
+    gets byte 127.  Element 2j of a row is the low nibble of byte j (the
+    layout of torch.float4_e2m1fn_x2).  The dequantized weight is
+    e2m1(code) * 2^(wscale - 127)."""
+    _check_w4_weight(weight)   # the same shapes and dtypes as int4
+    return ref.quantize_mxfp4_ref(weight)
+
+
+def dequantize_mxfp4(qweight, wscale):
+    """The dequantized weight e2m1(code) * 2^(wscale - 127), fp32 [N, K]."""
+    _check_mxfp4_weight(qweight, wscale)
+    return ref.dequantize_mxfp4_ref(qweight, wscale)
+
+
+def linear_mxfp4_q(xq, xscale, qweight, wscale):
+    """The GEMM of `linear_mxfp4` alone: xq float8_e4m3fn [M, K] with xscale
+    fp32 [M] (quantize_rows_fp8) against qweight / wscale (quantize_mxfp4),
+    y[m, n] = bf16((sum_k xq[m,k] * w_hat[n,k]) * xscale[m]), [M, N] bf16.
+    On the GPU mxfp4_gemm_kernel; elsewhere the same arithmetic in torch
+    ops."""
+    N, K = _check_mxfp4_weight(qweight, wscale)
+    if xq.dtype is not torch.float8_e4m3fn:
+        raise TypeError(f"xq must be float8_e4m3fn, got {xq.dtype}")
+    if xscale.dtype is not torch.float32:
+        raise TypeError(f"xscale must be fp32, got {xscale.dtype}")
+    if xq.dim() != 2 or xq.shape[1] != K:
+        raise ValueError(f"xq must be [M, K={K}], got {tuple(xq.shape)}")
+    M = xq.shape[0]
+    if M == 0:
+        raise ValueError(f"xq has no rows: {tuple(xq.shape)}")
+    if tuple(xscale.shape) != (M,):
+        raise ValueError(f"xscale must be [M={M}], got "
+                         f"{tuple(xscale.shape)}")
+    for name, t in (("xq", xq), ("xscale", xscale)):
+        if t.device != qweight.device:
+            raise ValueError(f"{name} is on {t.device}, qweight on "
+                             f"{qweight.device}")
+    if not xq.is_cuda:
+        return ref.linear_mxfp4_q_ref(xq, xscale, qweight, wscale)
+    ext = _sync_wrapped(get_ext(required=True))
+    return ext.linear_mxfp4(xq.contiguous(), xscale.contiguous(), qweight,
+                            wscale)
+
+
+def linear_mxfp4(x, qweight, wscale):
+    """x [..., K] . w_hat^T with MXFP4 weights (quantize_mxfp4) and x
+    quantized per row to e4m3 at run time, K2x.
+
+    On the GPU in bf16 without grad this is `quantize_rows_fp8` followed by
+    the csrc/linear_mxfp4.hip GEMM: the fp4 bytes and their E8M0 block
+    scales are the operands of the block-scaled MFMA as loaded, the row
+    scale multiplies the fp32 sum, one rounding to bf16; K is split
+    deterministically, the result of a row is bitwise reproducible and
+    independent of the other rows, and the call captures into a graph.
+    Anywhere else it is the reference composition on the same device
+    (quantize rows, dequantize both, `linear`).  Returns [..., N] in x's
+    dtype."""
+    N, K = _check_mxfp4_weight(qweight, wscale)
+    _check_fp8_x(x, K, qweight)
+    ext = _ext_for(x)
+    if ext is None:
+        return ref.linear_mxfp4_ref(x, qweight, wscale)
+    xq, xs = ext.quantize_rows_fp8(x.reshape(-1, K).contiguous())
+    y = ext.linear_mxfp4(xq, xs, qweight, wscale)
+    return y.view(*x.shape[:-1], N)

@@ -688,6 +688,103 @@ def linear_fp8_bound_ref(xq, xscale, qweight, wscale):
     return want, 2.0 ** -7 * want.abs() + 2.0 ** -10 * A
 
 
+# ---- MXFP4 weight linear.  Format (csrc/linear_mxfp4.hip; OCP MX v1.0):
+# qweight uint8 [N, K/2], two e2m1 codes a byte with element 2j in the low
+# nibble of byte j; wscale uint8 [N, K/32], one E8M0 byte per 32 k,
+# w_hat = e2m1(code) * 2^(byte - 127).  Activations are quantized per row to
+# e4m3 as for fp8.
+
+MX_BLOCK = 32
+# value of code c; codes 8..15 are the negatives, 8 is -0
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)
+
+
+def _e2m1_codes(v):
+    """v fp64, already divided by the block scale -> uint8 codes: round to
+    nearest, ties to the even code, saturating at +-6; the sign bit is v's
+    (a negative that rounds to zero is code 8).  torch.round rounds halves
+    to even, and in each of the three binades the even multiples of the
+    step are the even codes."""
+    a = v.abs().clamp(max=6.0)
+    mag = torch.where(a < 2, torch.round(a * 2),                 # step 0.5
+                      torch.where(a < 4, torch.round(a) + 2,     # step 1
+                                  torch.round(a / 2) + 4))       # step 2
+    return (mag + 8 * (v < 0)).to(torch.uint8)
+
+
+def quantize_mxfp4_ref(weight):
+    """weight [N, K] -> (qweight uint8 [N, K/2], wscale uint8 [N, K/32]).
+    Per block of 32 along K: e = floor(log2(amax)) - 2 clamped to
+    [-127, 127] (2 = e2m1's largest exponent), byte = e + 127, codes =
+    rne_e2m1(w / 2^e); an all-zero block gets byte 127 and zero codes.  The
+    division by a power of two is exact (done in fp64, where no quotient of
+    an fp32 weight is subnormal)."""
+    N, K = weight.shape
+    w = weight.detach().double().view(N, K // MX_BLOCK, MX_BLOCK)
+    amax = w.abs().amax(-1)
+    # frexp: amax = m * 2^ex with m in [0.5, 1), so floor(log2) = ex - 1
+    e = (torch.frexp(amax)[1] - 1 - 2).clamp(-127, 127)
+    e = torch.where(amax == 0, torch.zeros_like(e), e)
+    codes = _e2m1_codes(torch.ldexp(w, -e.unsqueeze(-1))).view(N, K)
+    qweight = codes[:, 0::2] | (codes[:, 1::2] << 4)
+    return qweight.contiguous(), (e + 127).to(torch.uint8)
+
+
+def dequantize_mxfp4_ref(qweight, wscale):
+    """w_hat fp32 [N, K], exact for block exponents up to 125 (6 * 2^126
+    and above overflow fp32; a finite fp32 weight never quantizes there)."""
+    N = qweight.shape[0]
+    c = torch.stack([qweight & 15, qweight >> 4], -1).view(N, -1, MX_BLOCK)
+    # code = sign | exponent (2 bits) | mantissa bit, in arithmetic (no
+    # table, so nothing is copied to the device and the call can be captured
+    # into a graph): |value| = (2 * (ex > 0) + man) * 2^(max(ex, 1) - 2)
+    c = c.int()
+    ex, man = (c >> 1) & 3, c & 1
+    sig = ((2 * (ex > 0) + man) * (1 - 2 * (c >> 3))).float()
+    e = ex.clamp(min=1) - 2 + wscale.int().unsqueeze(-1) - 127
+    return torch.ldexp(sig, e).view(N, -1)
+
+
+def linear_mxfp4_q_ref(xq, xscale, qweight, wscale):
+    """[M, N] bf16: the fp32 product of the e4m3 values and w_hat, then
+    acc * xscale[m] and one rounding, the kernel's order."""
+    acc = xq.float() @ dequantize_mxfp4_ref(qweight, wscale).T
+    return (acc * xscale.unsqueeze(-1)).to(torch.bfloat16)
+
+
+def linear_mxfp4_ref(x, qweight, wscale):
+    """x [..., K] . w_hat^T with x quantized per row (quantize_rows_fp8_ref):
+    both sides are dequantized, cast to x's dtype (w_hat exactly, it has two
+    mantissa bits) and go through `linear`.  The gradient passes the row
+    quantization straight through to x."""
+    xq, xscale = quantize_rows_fp8_ref(x)
+    xh = dequantize_fp8_ref(xq, xscale).to(x.dtype)
+    if x.requires_grad:
+        xh = x + (xh - x).detach()
+    w = dequantize_mxfp4_ref(qweight, wscale).to(x.dtype)
+    return torch.nn.functional.linear(xh, w)
+
+
+def linear_mxfp4_bound_ref(xq, xscale, qweight, wscale):
+    """(want, tol) in fp64, [M, N]: linear_fp8_bound_ref with w_hat in place
+    of wscale * q.
+
+      want   (xq . w_hat^T) * xscale[m]
+      A      (|xq| . |w_hat|^T) * xscale[m]
+      tol    2^-7 * |want| + 2^-10 * A
+
+    The same derivation: one bf16 rounding (2^-8 * |want|, doubled) and
+    worst-case fp32 accumulation of K * 2^-24 * A up to K = 16384.  The
+    block scales are powers of two and add no error."""
+    a = xq.detach().cpu().double()
+    w = dequantize_mxfp4_ref(qweight.detach().cpu(),
+                             wscale.detach().cpu()).double()
+    sc = xscale.detach().cpu().double().unsqueeze(-1)
+    want = (a @ w.T) * sc
+    A = (a.abs() @ w.abs().T) * sc
+    return want, 2.0 ** -7 * want.abs() + 2.0 ** -10 * A
+
+
 # ---- multi-LoRA delta (csrc/lora.hip).  bank_a [S, R, K], bank_b [S, O, R]
 # with alpha / r folded into bank_b; idx [N] picks a row's adapter, an id
 # outside [0, S) means "no adapter".

@@ -21,8 +21,13 @@ dequantize-then-GEMM lane of Fp8Linear.  With --sweep it also times the fp8
 GEMM under forced split counts (M = 1, 32) and with one against two M-tiles
 per wave (M >= 64).
 
+--mxfp4 adds the MXFP4 arms (csrc/linear_mxfp4.hip) in the same way:
+"mxfp4", the public op ops.linear_mxfp4; "mxfp4gemm", the GEMM alone;
+"mxfp4deq", the dequantize-then-GEMM lane of Mxfp4Linear; with --sweep the
+GEMM under forced split counts and with one against two M-tiles per wave.
+
 Usage: python scripts/bench_linear_w4.py [--rows 1 8 32] [--sweep] [--fp8]
-                                         [--out F]
+                                         [--mxfp4] [--out F]
 """
 import argparse
 import os
@@ -128,7 +133,48 @@ def fp8_arms(ext, OF, name, N, K, M, x, fq, fs, sweep, out):
     return graphs
 
 
-def bench_shape(name, N, K, rows, sweep, out, fp8=False):
+def mx_bytes(N, K):
+    return N * K // 2 + N * (K // 32)
+
+
+def mxfp4_arms(ext, OF, name, N, K, M, x, mq, ms, sweep, out):
+    """The MXFP4 graphs of one (shape, M), and the sweep lines."""
+    Rm = len(mq)
+    xq, xs = OF.quantize_rows_fp8(x)
+
+    def deq(i):
+        w = OF.dequantize_mxfp4(mq[i], ms[i]).to(torch.bfloat16)
+        return torch.nn.functional.linear(x, w)
+
+    graphs = {
+        "mxfp4": (capture(lambda i: OF.linear_mxfp4(x, mq[i], ms[i]), Rm), Rm),
+        "mxfp4gemm": (capture(
+            lambda i: ext.linear_mxfp4(xq, xs, mq[i], ms[i]), Rm), Rm),
+        "mxfp4deq": (capture(deq, 2), 2),
+    }
+    if not sweep:
+        return graphs
+    if M in (1, 32):
+        nch = K // 128
+        cands = sorted({min(nch, max(1, -(-t // (N // 64))))
+                        for t in (128, 256, 512, 1024, 2048, 4096)})
+        sg = {f"S={s}": (capture(
+            lambda i, s=s: ext.linear_mxfp4(xq, xs, mq[i], ms[i], s), Rm), Rm)
+            for s in cands}
+        out(f"{name:8s} M={M:4d} mxfp4 gemm splits sweep: " + "  ".join(
+            f"{n} ({int(n[2:]) * (N // 64)} waves) {v[0]:.1f} us"
+            for n, v in time_graphs(sg).items()))
+    if M >= 32:
+        mg = {f"MT={t}": (capture(
+            lambda i, t=t: ext.linear_mxfp4(xq, xs, mq[i], ms[i], 0, t), Rm),
+            Rm) for t in (1, 2)}
+        out(f"{name:8s} M={M:4d} mxfp4 gemm one vs two M-tiles: " + "  ".join(
+            f"{n} {v[0]:.1f} us [{v[1]:.1f}..{v[2]:.1f}]"
+            for n, v in time_graphs(mg).items()))
+    return graphs
+
+
+def bench_shape(name, N, K, rows, sweep, out, fp8=False, mxfp4=False):
     from modal_examples_amd.ops import functional as OF
     from modal_examples_amd.ops._build import get_ext
 
@@ -152,6 +198,16 @@ def bench_shape(name, N, K, rows, sweep, out, fp8=False):
               for _ in range(Rf)]
         out(f"## {name}: fp8 {(N * K + 4 * N) / 1e6:.1f} MB x {Rf} copies; "
             f"split rule S={ext.linear_fp8_splits(1, N, K)}")
+    if mxfp4:
+        Rm = copies_for(mx_bytes(N, K))
+        mq = [torch.randint(0, 256, (N, K // 2), device="cuda",
+                            dtype=torch.uint8, generator=gen)
+              for _ in range(Rm)]
+        ms = [torch.randint(116, 123, (N, K // 32), device="cuda",
+                            dtype=torch.uint8, generator=gen)
+              for _ in range(Rm)]
+        out(f"## {name}: mxfp4 {mx_bytes(N, K) / 1e6:.1f} MB x {Rm} copies; "
+            f"split rule S={ext.linear_mxfp4_splits(1, N, K)}")
     with torch.no_grad():
         for M in rows:
             x = torch.randn(M, K, device="cuda", generator=gen).to(torch.bfloat16)
@@ -169,10 +225,14 @@ def bench_shape(name, N, K, rows, sweep, out, fp8=False):
             if fp8:
                 graphs.update(fp8_arms(ext, OF, name, N, K, M, x, fq, fs,
                                        sweep, out))
+            if mxfp4:
+                graphs.update(mxfp4_arms(ext, OF, name, N, K, M, x, mq, ms,
+                                         sweep, out))
             res = time_graphs(graphs)
             nbytes = {"w4": w4_bytes(N, K), "bf16": 2 * N * K,
                       "dequant": w4_bytes(N, K)}
             nbytes.update({n: N * K + 4 * N for n in res if n[:3] == "fp8"})
+            nbytes.update({n: mx_bytes(N, K) for n in res if n[:5] == "mxfp4"})
             line = f"{name:8s} M={M:4d}"
             for n in res:
                 med, lo, hi = res[n]
@@ -182,6 +242,12 @@ def bench_shape(name, N, K, rows, sweep, out, fp8=False):
             if fp8:
                 line += (f" bf16/fp8 {res['bf16'][0] / res['fp8'][0]:.2f}x"
                          f" w4/fp8 {res['w4'][0] / res['fp8'][0]:.2f}x")
+            if mxfp4:
+                line += (f" bf16/mxfp4 {res['bf16'][0] / res['mxfp4'][0]:.2f}x"
+                         f" w4/mxfp4 {res['w4'][0] / res['mxfp4'][0]:.2f}x")
+                if fp8:
+                    line += (f" fp8gemm/mxfp4gemm "
+                             f"{res['fp8gemm'][0] / res['mxfp4gemm'][0]:.2f}x")
             out(line)
             del graphs
             if sweep and M in (1, 32):
@@ -199,6 +265,8 @@ def bench_shape(name, N, K, rows, sweep, out, fp8=False):
     del qw, sc, wb
     if fp8:
         del fq, fs
+    if mxfp4:
+        del mq, ms
     torch.cuda.empty_cache()
 
 
@@ -208,6 +276,7 @@ def main():
     ap.add_argument("--shapes", nargs="+", default=[s[0] for s in SHAPES])
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--fp8", action="store_true")
+    ap.add_argument("--mxfp4", action="store_true")
     ap.add_argument("--out", default=None, help="also append the lines here")
     a = ap.parse_args()
     if not torch.cuda.is_available():
@@ -224,7 +293,7 @@ def main():
         f">= {ROTATE_BYTES >> 20} MB; GB/s = the arm's weight bytes / time")
     for name, N, K in SHAPES:
         if name in a.shapes:
-            bench_shape(name, N, K, a.rows, a.sweep, out, a.fp8)
+            bench_shape(name, N, K, a.rows, a.sweep, out, a.fp8, a.mxfp4)
 
 
 if __name__ == "__main__":

@@ -90,6 +90,13 @@ OCCUPANCY_FLOORS = {
     "fp8_gemm_kernelILi2E": 2,
     "fp8_reduce_kernel": 8,
     "fp8_quant_rows_kernel": 8,   # both: row in registers, row read twice
+    # mxfp4_gemm_kernel<MT>: two register sets of a 128-deep chunk (34 / 50
+    # registers each for MT = 1 / 2: the fp4 weights are half the fp8
+    # kernel's, plus a scale pair per weight row) beside 32 / 64
+    # accumulators; two waves per SIMD as fp8_gemm_kernel
+    "mxfp4_gemm_kernelILi1E": 2,
+    "mxfp4_gemm_kernelILi2E": 2,
+    "mxfp4_reduce_kernel": 8,
 }
 
 
