@@ -12,6 +12,12 @@
 # experts run on the fused lane (`moe_impl="fused"`, ops/csrc/moe.hip):
 # routing, the grouped expert GEMMs and the combine stay on the device, so
 # decode replays one captured graph like a dense model.
+#
+# `MOE_EXPERT_DTYPE=int4` or `mxfp4` holds the experts quantized (0.52 / 0.53
+# bytes per weight) and decodes on the grouped int4 / block-scaled fp4 GEMMs
+# (docs/ENGINE.md, "expert_dtype"); GPU only, the default stays bf16.
+
+import os
 
 import modal_examples_amd as modal
 
@@ -35,6 +41,9 @@ class MoELLM:
         eng = LlamaEngine(cfg, device="cuda" if gpu else "cpu",
                           dtype=torch.bfloat16 if gpu else torch.float32,
                           moe_impl="fused" if gpu else None, use_graph=gpu,
+                          expert_dtype=(os.environ.get("MOE_EXPERT_DTYPE",
+                                                       "bf16")
+                                        if gpu else "bf16"),
                           kv_blocks=None if gpu else 128, prefix_cache=True)
         self.cfg = cfg
         self.engine = eng
@@ -43,10 +52,13 @@ class MoELLM:
     @modal.method()
     def generate(self, prompt: str, max_tokens: int = 12) -> dict:
         text = self.server.generate(prompt, max_tokens=max_tokens)
-        total = sum(p.numel() for p in self.engine.model.parameters())
         # active params per token: dense layers + top-k of the expert pool
+        # (counted from the shapes: packed experts are buffers, not params)
         moe = self.engine.model.blocks[0].moe
-        expert_p = (moe.gate_up[0].numel() + moe.down[0].numel())
+        expert_p = 3 * moe.ffn_dim * moe.dim
+        total = sum(p.numel() for p in self.engine.model.parameters())
+        if moe.expert_dtype != "bf16":
+            total += self.cfg.n_layers * self.cfg.n_experts * expert_p
         active = total - self.cfg.n_layers * (
             self.cfg.n_experts - moe.top_k) * expert_p
         return {"text_words": len(text.split()), "total_params": total,

@@ -174,7 +174,15 @@ class LlamaEngine:
         Mxfp4Linear.M_KERNEL rows run on the csrc/linear_mxfp4.hip kernel
         inside the decode graph, and everything else is as for "fp8".
 
-        expert_dtype: "bf16" or "int4"; None keeps cfg.expert_dtype.  "int4"
+        expert_dtype: "bf16", "int4" or "mxfp4"; None keeps cfg.expert_dtype.
+        "mxfp4" holds the experts as OCP MX fp4 with one E8M0 scale byte per
+        32 inputs (ops.quantize_mxfp4_experts): 0.53 bytes per expert weight;
+        batches up to MoEFFN.N_KERNEL_MXFP4 tokens run on the grouped
+        block-scaled MFMA kernels of csrc/moe_mxfp4.hip (ops.moe_ffn_mxfp4),
+        which quantize x per token and h per (token, expert) row to e4m3,
+        inside the decode graph; larger ones take the dequantize-and-loop
+        lane with unquantized activations.  Everything else said for "int4"
+        below holds for it.  "int4"
         holds the experts of every MoE block as 4-bit weights with one bf16
         scale per 128 inputs (ops.quantize_w4_experts; model.MoEFFN): 0.52
         bytes per expert weight instead of 2, with the router, qkv and o_proj
@@ -215,22 +223,23 @@ class LlamaEngine:
                              f"got {weight_dtype!r}")
         if weight_dtype != "bf16" and self.cfg.n_experts > 0:
             raise ValueError(f"weight_dtype={weight_dtype!r} does not cover "
-                             f"MoE experts; use weight_dtype='bf16' for an "
-                             f"MoE config")
+                             f"MoE models; use weight_dtype='bf16' and "
+                             f"expert_dtype='int4'|'mxfp4' for an MoE config")
         self.weight_dtype = weight_dtype
         if expert_dtype is None:
             expert_dtype = self.cfg.expert_dtype
         if expert_dtype not in EXPERT_DTYPES:
             raise ValueError(f"expert_dtype must be one of {EXPERT_DTYPES}, "
                              f"got {expert_dtype!r}")
-        if expert_dtype == "int4":
+        if expert_dtype != "bf16":
             if self.cfg.n_experts <= 0:
-                raise ValueError("expert_dtype='int4' needs an MoE config "
-                                 "(n_experts > 0); weight_dtype='int4' is "
-                                 "the dense model's knob")
+                raise ValueError(f"expert_dtype={expert_dtype!r} needs an MoE "
+                                 f"config (n_experts > 0); weight_dtype="
+                                 f"{expert_dtype!r} is the dense model's knob")
             if self.cfg.moe_impl != "fused":
-                raise ValueError("expert_dtype='int4' needs moe_impl='fused',"
-                                 f" got moe_impl={self.cfg.moe_impl!r}")
+                raise ValueError(f"expert_dtype={expert_dtype!r} needs "
+                                 f"moe_impl='fused', got "
+                                 f"moe_impl={self.cfg.moe_impl!r}")
         self.cfg = dataclasses.replace(self.cfg, expert_dtype=expert_dtype)
         self.expert_dtype = expert_dtype
         self.tp = tp
@@ -288,7 +297,7 @@ class LlamaEngine:
                 self.model = LlamaModel(
                     dataclasses.replace(self.cfg, expert_dtype="bf16"),
                     tp=tp).to(self.device, dtype)
-            if weight_dtype != "bf16" or expert_dtype == "int4":
+            if weight_dtype != "bf16" or expert_dtype != "bf16":
                 if weight_dtype == "int4":
                     quantize_llama_(self.model)
                 elif weight_dtype == "fp8":
@@ -296,7 +305,7 @@ class LlamaEngine:
                 elif weight_dtype == "mxfp4":
                     quantize_llama_mxfp4_(self.model)
                 else:
-                    quantize_llama_experts_(self.model)
+                    quantize_llama_experts_(self.model, expert_dtype)
                 if self.device.type == "cuda":
                     # hand the bf16 projections back before the pool is sized
                     torch.cuda.empty_cache()
@@ -406,9 +415,10 @@ class LlamaEngine:
         quantized on the device, and so it is with weight_dtype="fp8" and
         "mxfp4" (files that already hold fp8 or mxfp4 weights are refused).  The same holds for
         expert_dtype: a file
-        with `.gate_up_q` keys defaults it to "int4" and refuses "bf16", and
-        a bf16 file with expert_dtype="int4" is quantized on the device after
-        loading."""
+        with `.gate_up_q` keys defaults it to what they hold ("int4" for
+        int32 words, "mxfp4" for uint8 bytes) and refuses anything else, and
+        a bf16 file with expert_dtype="int4" or "mxfp4" is quantized on the
+        device after loading."""
         import threading
 
         from ...gpu import fastload
@@ -426,13 +436,17 @@ class LlamaEngine:
         if packed and kw["weight_dtype"] != "int4":
             raise ValueError(f"{path} holds int4 weights; it cannot boot a "
                              f"weight_dtype={kw['weight_dtype']!r} engine")
-        packed_experts = any(k.endswith(".gate_up_q") for k in header)
+        # the packed words' dtype is the format: int32 int4, uint8 mxfp4
+        held = [m["dtype"] for k, m in header.items()
+                if k.endswith(".gate_up_q")]
+        packed_experts = bool(held)
         if packed_experts:
-            kw.setdefault("expert_dtype", "int4")
-            if kw["expert_dtype"] != "int4":
-                raise ValueError(f"{path} holds int4 experts; it cannot boot "
-                                 f"an expert_dtype={kw['expert_dtype']!r} "
-                                 f"engine")
+            kind = "mxfp4" if held[0] == "U8" else "int4"
+            kw.setdefault("expert_dtype", kind)
+            if kw["expert_dtype"] != kind:
+                raise ValueError(f"{path} holds {kind} experts; it cannot "
+                                 f"boot an expert_dtype="
+                                 f"{kw['expert_dtype']!r} engine")
         tp = kw.get("tp")
         if packed and tp is not None and tp.world > 1:
             raise ValueError("loading an int4 checkpoint under tensor "
@@ -467,8 +481,8 @@ class LlamaEngine:
             sd = quantize_llama_fp8_state(sd)
         if eng.weight_dtype == "mxfp4":
             sd = quantize_llama_mxfp4_state(sd)
-        if eng.expert_dtype == "int4" and not packed_experts:
-            sd = quantize_llama_expert_state(sd)
+        if eng.expert_dtype != "bf16" and not packed_experts:
+            sd = quantize_llama_expert_state(sd, eng.expert_dtype)
         eng.model.load_state_dict(sd, assign=True)
         return eng
 

@@ -39,7 +39,7 @@ class LlamaConfig:
     n_experts: int = 0   # >0: MoE FFN (Mixtral/DeepSeek-class)
     experts_per_tok: int = 2
     moe_impl: str = "loop"  # MoEFFN forward: "loop" or "fused" (ops.moe_ffn)
-    expert_dtype: str = "bf16"  # MoE expert weights: "bf16" or "int4"
+    expert_dtype: str = "bf16"  # MoE expert weights: "bf16", "int4", "mxfp4"
 
     @staticmethod
     def llama3_8b() -> "LlamaConfig":
@@ -59,7 +59,7 @@ class LlamaConfig:
 
 
 WEIGHT_DTYPES = ("bf16", "int4", "fp8", "mxfp4")
-EXPERT_DTYPES = ("bf16", "int4")
+EXPERT_DTYPES = ("bf16", "int4", "mxfp4")
 
 
 class QuantLinear(nn.Module):
@@ -370,23 +370,34 @@ def quantize_llama_mxfp4_state(state: dict) -> dict:
     return out
 
 
-def quantize_llama_experts_(model: "LlamaModel") -> "LlamaModel":
-    """Quantize the experts of every MoE block in place
-    (MoEFFN.quantize_experts_), one matrix at a time so the bf16 copy of each
-    is released as it goes.  Router, attention projections, embedding, norms
-    and lm_head stay as they are."""
+# the packed expert formats: their quantizers, and the dtype of the _q buffer,
+# which tells the formats apart in a module and in a file
+_EXPERT_QUANTIZERS = {"int4": OF.quantize_w4_experts,
+                      "mxfp4": OF.quantize_mxfp4_experts}
+_EXPERT_Q_DTYPES = {torch.int32: "int4", torch.uint8: "mxfp4"}
+
+
+def quantize_llama_experts_(model: "LlamaModel",
+                            expert_dtype: str = "int4") -> "LlamaModel":
+    """Quantize the experts of every MoE block in place to `expert_dtype`
+    ("int4" or "mxfp4"; MoEFFN.quantize_experts_), one matrix at a time so the
+    bf16 copy of each is released as it goes.  Router, attention projections,
+    embedding, norms and lm_head stay as they are."""
     if model.cfg.n_experts <= 0:
-        raise ValueError("expert_dtype='int4' needs an MoE config "
+        raise ValueError(f"expert_dtype={expert_dtype!r} needs an MoE config "
                          "(n_experts > 0)")
     for blk in model.blocks:
-        blk.moe.quantize_experts_()
-    model.cfg = dataclasses.replace(model.cfg, expert_dtype="int4")
+        blk.moe.quantize_experts_(expert_dtype)
+    model.cfg = dataclasses.replace(model.cfg, expert_dtype=expert_dtype)
     return model
 
 
-def quantize_llama_expert_state(state: dict) -> dict:
+def quantize_llama_expert_state(state: dict,
+                                expert_dtype: str = "int4") -> dict:
     """A bf16 state dict of an MoE LlamaModel with every block's
-    `moe.gate_up` / `moe.down` replaced by its `_q` / `_s` pair."""
+    `moe.gate_up` / `moe.down` replaced by its `_q` / `_s` pair in
+    `expert_dtype` ("int4" or "mxfp4")."""
+    quantize = _EXPERT_QUANTIZERS[expert_dtype]
     out = {}
     for k, v in state.items():
         parts = k.split(".")
@@ -394,8 +405,7 @@ def quantize_llama_expert_state(state: dict) -> dict:
                 and parts[3] in ("gate_up", "down")):
             if v.dtype not in (torch.bfloat16, torch.float32):
                 v = v.float()
-            out[k + "_q"], out[k + "_s"] = OF.quantize_w4_experts(
-                v.contiguous())
+            out[k + "_q"], out[k + "_s"] = quantize(v.contiguous())
         else:
             out[k] = v
     return out
@@ -424,7 +434,8 @@ class LlamaBlock(nn.Module):
             # a shard whose K is no multiple of 128 raises here
             if cfg.n_experts > 0:
                 raise ValueError(f"weight_dtype={weight_dtype!r} does not "
-                                 f"cover MoE experts")
+                                 f"cover MoE models; their experts take "
+                                 f"expert_dtype='int4'|'mxfp4'")
             quant = {"int4": QuantLinear, "fp8": Fp8Linear,
                      "mxfp4": Mxfp4Linear}[weight_dtype]
 
@@ -665,7 +676,20 @@ class MoEFFN(nn.Module):
     its GEMMs; in bf16 that rounds every scale * q to bf16, like
     QuantLinear's prefill lane, so the two lanes differ by that rounding (in
     fp32 they are the same products).  The prefill lane reads the routing
-    back to the host; decode stays under N_KERNEL and captures."""
+    back to the host; decode stays under N_KERNEL and captures.
+
+    expert_dtype="mxfp4" (impl="fused" only) holds them as OCP MX fp4: two
+    e2m1 codes a byte with one E8M0 scale byte per 32 inputs
+    (ops.quantize_mxfp4_experts), 0.53 bytes per weight, in four uint8
+    buffers of the same names — the dtype of gate_up_q tells the two packed
+    formats apart.  Again two lanes.  Up to N_KERNEL_MXFP4 tokens the forward
+    is ops.moe_route -> ops.moe_ffn_mxfp4 (csrc/moe_mxfp4.hip), which
+    quantizes x per token and h per (token, expert) row to e4m3 and feeds
+    the packed bytes to the block-scaled MFMA as loaded.  Above that it is
+    the same dequantize-and-loop lane as int4's: w_hat has two mantissa bits
+    and is exact in bf16, and the activations are NOT quantized there, as in
+    Mxfp4Linear's prefill lane, so the two lanes differ by the activation
+    quantization."""
 
     IMPLS = ("loop", "fused")
 
@@ -676,6 +700,13 @@ class MoEFFN(nn.Module):
     # (3147 / 5419 us; 1596 / 5092 at 2048).  4096 is the largest measured
     # count, and it is on the kernel's side; the crossover lies above it.
     N_KERNEL = 4096
+    # the same for the mxfp4 kernel lane, from its own measurement at the same
+    # shape (profiles/moe_ffn_mxfp4.txt, "crossover" lines): dequantizing
+    # eight experts in torch ops costs about 16 ms whatever N, and the kernel
+    # lane is far ahead at every measured count (2080 / 16844 us at 4096
+    # tokens, 1158 / 16483 at 2048).  4096 is the largest measured count; the
+    # crossover lies above it.
+    N_KERNEL_MXFP4 = 4096
 
     def __init__(self, dim: int, ffn_dim: int, n_experts: int, top_k: int,
                  impl: str = "loop", expert_dtype: str = "bf16"):
@@ -691,65 +722,89 @@ class MoEFFN(nn.Module):
         self.dim, self.ffn_dim = dim, ffn_dim
         self.n_experts, self.top_k = n_experts, top_k
         self.router = nn.Linear(dim, n_experts, bias=False)
-        if expert_dtype == "int4":
-            # empty packed buffers, for loading a quantized state
-            self._check_int4()
+        if expert_dtype != "bf16":
+            # empty packed buffers, for loading a quantized state: zero
+            # weights under unit scales (bf16 1, E8M0 byte 127)
+            self._check_packed(expert_dtype)
             self.gate_up = self.down = None
+            if expert_dtype == "int4":
+                qdt, per_q, per_s, sdt, one = (torch.int32, 8, 128,
+                                               torch.bfloat16, 1)
+            else:
+                qdt, per_q, per_s, sdt, one = (torch.uint8, 2, 32,
+                                               torch.uint8, 127)
             self._set_packed(
-                torch.zeros(n_experts, 2 * ffn_dim, dim // 8, dtype=torch.int32),
-                torch.ones(n_experts, 2 * ffn_dim, dim // 128,
-                           dtype=torch.bfloat16),
-                torch.zeros(n_experts, dim, ffn_dim // 8, dtype=torch.int32),
-                torch.ones(n_experts, dim, ffn_dim // 128,
-                           dtype=torch.bfloat16))
+                torch.zeros(n_experts, 2 * ffn_dim, dim // per_q, dtype=qdt),
+                torch.full((n_experts, 2 * ffn_dim, dim // per_s), one,
+                           dtype=sdt),
+                torch.zeros(n_experts, dim, ffn_dim // per_q, dtype=qdt),
+                torch.full((n_experts, dim, ffn_dim // per_s), one,
+                           dtype=sdt))
             return
         self.gate_up = nn.Parameter(
             torch.empty(n_experts, 2 * ffn_dim, dim).normal_(std=0.02))
         self.down = nn.Parameter(
             torch.empty(n_experts, dim, ffn_dim).normal_(std=0.02))
 
-    def _check_int4(self):
+    def _check_packed(self, expert_dtype):
         if self.impl != "fused":
-            raise ValueError("expert_dtype='int4' needs moe_impl='fused', got "
-                             f"moe_impl={self.impl!r}")
+            raise ValueError(f"expert_dtype={expert_dtype!r} needs "
+                             f"moe_impl='fused', got moe_impl={self.impl!r}")
         if self.dim % 128 or self.ffn_dim % 128:
-            raise ValueError(f"expert_dtype='int4' needs dim={self.dim} and "
-                             f"ffn_dim={self.ffn_dim} to be multiples of the "
-                             f"int4 group size 128")
+            raise ValueError(f"expert_dtype={expert_dtype!r} needs dim="
+                             f"{self.dim} and ffn_dim={self.ffn_dim} to be "
+                             f"multiples of 128 (the int4 group, the mxfp4 "
+                             f"kernel's chunk)")
 
     def _set_packed(self, gate_up_q, gate_up_s, down_q, down_s):
         for name, t in (("gate_up_q", gate_up_q), ("gate_up_s", gate_up_s),
                         ("down_q", down_q), ("down_s", down_s)):
             self.register_buffer(name, t)
-        self.expert_dtype = "int4"
+        self.expert_dtype = _EXPERT_Q_DTYPES[gate_up_q.dtype]
         self._scratch = {}
 
-    def quantize_experts_(self) -> "MoEFFN":
-        """Convert an initialised bf16-expert module in place, one matrix at
-        a time, and free the two Parameters."""
-        if self.expert_dtype == "int4":
+    def quantize_experts_(self, expert_dtype: str = "int4") -> "MoEFFN":
+        """Convert an initialised bf16-expert module in place to
+        `expert_dtype` ("int4" or "mxfp4"), one matrix at a time, and free
+        the two Parameters."""
+        if self.expert_dtype == expert_dtype:
             return self
-        self._check_int4()
+        if self.expert_dtype != "bf16" or expert_dtype not in _EXPERT_QUANTIZERS:
+            raise ValueError(f"cannot quantize {self.expert_dtype} experts to "
+                             f"{expert_dtype!r}")
+        self._check_packed(expert_dtype)
         packed = []
         for name in ("gate_up", "down"):
             w = getattr(self, name).detach()
             if w.dtype not in (torch.bfloat16, torch.float32):
                 w = w.float()
             setattr(self, name, None)  # drops the Parameter
-            packed.extend(OF.quantize_w4_experts(w.contiguous()))
+            packed.extend(_EXPERT_QUANTIZERS[expert_dtype](w.contiguous()))
             del w
         self._set_packed(*packed)
         return self
 
+    def _load_from_state_dict(self, state_dict, prefix, *args, **kwargs):
+        # the buffers' dtype is the format: an int4 state does not load into
+        # mxfp4 buffers (copy_ would cast it silently), nor the reverse
+        q = state_dict.get(prefix + "gate_up_q")
+        if (q is not None and self.expert_dtype != "bf16"
+                and _EXPERT_Q_DTYPES.get(q.dtype) != self.expert_dtype):
+            raise ValueError(f"{prefix}gate_up_q is {q.dtype}: not an "
+                             f"{self.expert_dtype} expert state")
+        super()._load_from_state_dict(state_dict, prefix, *args, **kwargs)
+
     def _apply(self, fn, recurse=True):
         # module.to(dtype) casts every floating buffer; the scales are bf16
         # by format (a round trip through a wider type loses nothing)
+        # (mxfp4's four buffers are uint8, which no cast touches)
         super()._apply(fn, recurse)
         if self.expert_dtype == "int4":
             for name in ("gate_up_s", "down_s"):
                 t = getattr(self, name)
                 if t.dtype is not torch.bfloat16:
                     setattr(self, name, t.to(torch.bfloat16))
+        if self.expert_dtype != "bf16":
             self._scratch = {}
         return self
 
@@ -757,12 +812,14 @@ class MoEFFN(nn.Module):
         """Expert e's matrix `name` in `dtype`, in a scratch reused across
         experts and calls (one per matrix)."""
         q, s = getattr(self, name + "_q")[e], getattr(self, name + "_s")[e]
+        int4 = self.expert_dtype == "int4"
         buf = self._scratch.get(name)
         if buf is None or buf.dtype is not dtype or buf.device != q.device:
-            buf = torch.empty(q.shape[0], q.shape[1] * 8, dtype=dtype,
-                              device=q.device)
+            buf = torch.empty(q.shape[0], q.shape[1] * (8 if int4 else 2),
+                              dtype=dtype, device=q.device)
             self._scratch[name] = buf
-        buf.copy_(OF.dequantize_w4(q, s))
+        buf.copy_(OF.dequantize_w4(q, s) if int4
+                  else OF.dequantize_mxfp4(q, s))
         return buf
 
     def forward(self, x):
@@ -771,13 +828,16 @@ class MoEFFN(nn.Module):
         B, S, d = x.shape
         flat = x.reshape(-1, d)
         scores = self.router(flat).float()                  # [N, E]
-        int4 = self.expert_dtype == "int4"
-        if int4 and flat.shape[0] <= self.N_KERNEL:
-            w, idx = OF.moe_route(scores, self.top_k)
-            return OF.moe_ffn_w4(flat.contiguous(), self.gate_up_q,
-                                 self.gate_up_s, self.down_q, self.down_s, w,
-                                 idx).view(B, S, d)
-        if self.impl == "fused" and not int4:
+        packed = self.expert_dtype != "bf16"
+        if packed:
+            ffn, limit = ((OF.moe_ffn_w4, self.N_KERNEL)
+                          if self.expert_dtype == "int4"
+                          else (OF.moe_ffn_mxfp4, self.N_KERNEL_MXFP4))
+            if flat.shape[0] <= limit:
+                w, idx = OF.moe_route(scores, self.top_k)
+                return ffn(flat.contiguous(), self.gate_up_q, self.gate_up_s,
+                           self.down_q, self.down_s, w, idx).view(B, S, d)
+        if self.impl == "fused" and not packed:
             w, idx = OF.moe_route(scores, self.top_k)
             return OF.moe_ffn(flat.contiguous(), self.gate_up, self.down, w,
                               idx).view(B, S, d)
@@ -788,7 +848,7 @@ class MoEFFN(nn.Module):
             hit = (idx == e)                                # [N, k]
             rows = hit.any(-1).nonzero(as_tuple=True)[0]
             contrib = (w * hit).sum(-1)[rows].unsqueeze(-1)  # routed weight
-            if int4:
+            if packed:
                 gate_up = self._dequantized("gate_up", e, x.dtype)
                 down = self._dequantized("down", e, x.dtype)
             else:

@@ -35,6 +35,7 @@ HIP_SOURCES = [
     "lora.hip",
     "linear_fp8.hip",
     "linear_mxfp4.hip",
+    "moe_mxfp4.hip",
 ]
 
 # Per-source compiler flags beyond `common`; scripts/check_kernel_resources.py
@@ -59,6 +60,9 @@ EXTRA_FLAGS = {
     # no fast-math flag
     "linear_mxfp4.hip": ["-Xclang", "-target-feature", "-Xclang",
                          "-packed-fp32-ops"],
+    # the grouped form of the same kernel: the same flags
+    "moe_mxfp4.hip": ["-Xclang", "-target-feature", "-Xclang",
+                      "-packed-fp32-ops"],
 }
 
 

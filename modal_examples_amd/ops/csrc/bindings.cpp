@@ -101,6 +101,13 @@ int moe_ffn_w4_bf16(const void*, const void*, const void*, const void*,
                     const void*, const float*, const int*, int*, void*,
                     float*, void*, long long, int, int, int, int, int,
                     hipStream_t);
+// moe_ffn_mxfp4_plan / moe_ffn_mxfp4_bf16: as the w4 pair, with the row
+// quantization workspaces (xq, xs, hq, hs) beside sched, h and y
+int moe_ffn_mxfp4_plan(int, int);
+int moe_ffn_mxfp4_bf16(const void*, const void*, const void*, const void*,
+                       const void*, const float*, const int*, void*, float*,
+                       int*, void*, void*, float*, float*, void*, long long,
+                       int, int, int, int, int, hipStream_t);
 // linear_w4_plan: the K-slice count of a call, 0 for an unsupported shape;
 // linear_w4_bf16 returns 0 once launched, non-zero (nothing launched) else
 int linear_w4_plan(long long, int, int, int);
@@ -1118,6 +1125,96 @@ torch::Tensor moe_ffn_w4(torch::Tensor x, torch::Tensor gate_up_q,
   return out;
 }
 
+// moe_ffn over MXFP4 experts (format: linear_mxfp4.hip's with a leading
+// expert dimension): gate_up_q u8 [E,2F,d/2], gate_up_s u8 [E,2F,d/32], down_q
+// u8 [E,d,F/2], down_s u8 [E,d,F/32]; d and F multiples of 128.  down_splits
+// as in moe_ffn_w4 (tests and benchmarks only).  Returns [N,d] bf16.
+torch::Tensor moe_ffn_mxfp4(torch::Tensor x, torch::Tensor gate_up_q,
+                            torch::Tensor gate_up_s, torch::Tensor down_q,
+                            torch::Tensor down_s, torch::Tensor weights,
+                            torch::Tensor idx, int64_t down_splits) {
+  check_bf16(x, "x");
+  for (const torch::Tensor* t : {&gate_up_q, &gate_up_s, &down_q, &down_s})
+    TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
+                    t->scalar_type() == torch::kUInt8 && t->dim() == 3,
+                "moe_ffn_mxfp4: gate_up_q, gate_up_s, down_q and down_s must "
+                "be uint8 [E,R,*], contiguous, on GPU");
+  TORCH_CHECK(x.dim() == 2, "moe_ffn_mxfp4: x must be [N,dim]");
+  const int64_t N = x.size(0), d = x.size(1), E = gate_up_q.size(0),
+                F = down_q.size(2) * 2;
+  TORCH_CHECK(N >= 1, "moe_ffn_mxfp4: x has no rows");
+  TORCH_CHECK(d >= 128 && d % 128 == 0, "moe_ffn_mxfp4: x has dim=", d,
+              " (must be a multiple of 128)");
+  TORCH_CHECK(F >= 128 && F % 128 == 0, "moe_ffn_mxfp4: down_q has ffn_dim=",
+              F, " (must be a multiple of 128)");
+  TORCH_CHECK(E >= 1 && E <= 128, "moe_ffn_mxfp4: gate_up_q has E=", E,
+              " experts (supported: 1..128)");
+  TORCH_CHECK(gate_up_q.sizes() == torch::IntArrayRef({E, 2 * F, d / 2}) &&
+                  gate_up_s.sizes() == torch::IntArrayRef({E, 2 * F, d / 32}) &&
+                  down_q.sizes() == torch::IntArrayRef({E, d, F / 2}) &&
+                  down_s.sizes() == torch::IntArrayRef({E, d, F / 32}),
+              "moe_ffn_mxfp4: gate_up_q ", gate_up_q.sizes(), " / gate_up_s ",
+              gate_up_s.sizes(), " / down_q ", down_q.sizes(), " / down_s ",
+              down_s.sizes(), " do not agree on E=", E, " dim=", d,
+              " ffn_dim=", F);
+  TORCH_CHECK(idx.is_cuda() && idx.scalar_type() == torch::kInt32 &&
+                  idx.dim() == 2 && idx.size(0) == N && idx.is_contiguous(),
+              "moe_ffn_mxfp4: idx must be int32 [N,top_k] contiguous on GPU");
+  const int64_t k = idx.size(1);
+  TORCH_CHECK(k >= 1 && k <= 8 && k <= E, "moe_ffn_mxfp4: idx has top_k=", k,
+              " (supported: 1..min(E, 8), E=", E, ")");
+  TORCH_CHECK(weights.is_cuda() && weights.scalar_type() == torch::kFloat32 &&
+                  weights.sizes() == idx.sizes() && weights.is_contiguous(),
+              "moe_ffn_mxfp4: weights must be fp32 [N,top_k] contiguous on "
+              "GPU");
+  for (const torch::Tensor* t :
+       {&gate_up_q, &gate_up_s, &down_q, &down_s, &weights, &idx})
+    TORCH_CHECK(t->device() == x.device(),
+                "moe_ffn_mxfp4: all tensors must be on x's device");
+  TORCH_CHECK(N * k < (1ll << 30) && N * k * d < (1ll << 40),
+              "moe_ffn_mxfp4: x has too many rows (N=", N, ")");
+  TORCH_CHECK(down_splits >= 0 && down_splits < (1ll << 20),
+              "moe_ffn_mxfp4: down_splits out of range");
+  // the kernels read 16 B fragments (and 2 B scale pairs)
+  if ((uintptr_t)x.data_ptr() % 16) x = x.clone();
+  if ((uintptr_t)gate_up_q.data_ptr() % 16) gate_up_q = gate_up_q.clone();
+  if ((uintptr_t)down_q.data_ptr() % 16) down_q = down_q.clone();
+  if ((uintptr_t)gate_up_s.data_ptr() % 2) gate_up_s = gate_up_s.clone();
+  if ((uintptr_t)down_s.data_ptr() % 2) down_s = down_s.clone();
+  const int S = moe_ffn_mxfp4_plan((int)F, (int)down_splits);
+  TORCH_CHECK(S >= 1, "moe_ffn_mxfp4: ffn_dim=", F, " with down_splits=",
+              down_splits, " not supported by the kernel");
+  const int64_t tiles = moe_max_tiles(N, (int)k, (int)E);
+  auto bopt = x.options().dtype(torch::kUInt8);
+  auto fopt = x.options().dtype(torch::kFloat32);
+  auto xq = torch::empty({N, d}, bopt);
+  auto xs = torch::empty({N}, fopt);
+  auto sched =
+      torch::empty({tiles * 32 + tiles + 1}, x.options().dtype(torch::kInt32));
+  auto h = torch::empty({tiles * 32, F}, x.options());
+  auto hq = torch::empty({tiles * 32, F}, bopt);
+  auto hs = torch::empty({tiles * 32}, fopt);
+  auto y = torch::empty({S, N * k, d}, fopt);
+  auto out = torch::empty({N, d}, x.options());
+  int rc = moe_ffn_mxfp4_bf16(
+      x.data_ptr(), gate_up_q.data_ptr(), gate_up_s.data_ptr(),
+      down_q.data_ptr(), down_s.data_ptr(), weights.data_ptr<float>(),
+      idx.data_ptr<int>(), xq.data_ptr(), xs.data_ptr<float>(),
+      sched.data_ptr<int>(), h.data_ptr(), hq.data_ptr(),
+      hs.data_ptr<float>(), y.data_ptr<float>(), out.data_ptr(), N, (int)d,
+      (int)F, (int)E, (int)k, (int)down_splits, cur_stream());
+  TORCH_CHECK(rc == 0, "moe_ffn_mxfp4: shape not supported by the kernel (N=",
+              N, " dim=", d, " ffn_dim=", F, " E=", E, " top_k=", k, ")");
+  return out;
+}
+
+int64_t moe_ffn_mxfp4_splits(int64_t ffn_dim, int64_t down_splits) {
+  TORCH_CHECK(ffn_dim >= 0 && ffn_dim < (1ll << 31) && down_splits >= 0 &&
+                  down_splits < (1ll << 20),
+              "moe_ffn_mxfp4: size out of range");
+  return moe_ffn_mxfp4_plan((int)ffn_dim, (int)down_splits);
+}
+
 // x bf16 [M,K]; qweight int32 [N,K/8] or its uint8 view [N,K/2]; scales bf16
 // [N,K/128] (format: linear_w4.hip).  splits = 0 takes the kernel's split
 // rule; a positive value forces that many K slices (tests and benchmarks
@@ -1681,6 +1778,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x"), py::arg("gate_up_q"), py::arg("gate_up_s"),
         py::arg("down_q"), py::arg("down_s"), py::arg("weights"),
         py::arg("idx"), py::arg("down_splits") = 0);
+  m.def("moe_ffn_mxfp4", &moe_ffn_mxfp4,
+        "fused MoE FFN over MXFP4 experts (grouped block-scaled fp4 MFMA)",
+        py::arg("x"), py::arg("gate_up_q"), py::arg("gate_up_s"),
+        py::arg("down_q"), py::arg("down_s"), py::arg("weights"),
+        py::arg("idx"), py::arg("down_splits") = 0);
+  m.def("moe_ffn_mxfp4_splits", &moe_ffn_mxfp4_splits,
+        "K slices of moe_ffn_mxfp4's down GEMM for ffn_dim; 0 = unsupported",
+        py::arg("ffn_dim"), py::arg("down_splits") = 0);
   m.def("linear_w4", &linear_w4,
         "int4 weight-only linear: in-register dequant, MFMA, split-K",
         pybind11::arg("x"), pybind11::arg("qweight"), pybind11::arg("scales"),

@@ -115,12 +115,11 @@ DEV_INLINE void fp8_quant8(bf16x8 v, float scale, fp8_t* dst) {
 // 16384) and stays in registers between the max and the quantization, so x
 // is read once; otherwise the second pass reads it again.
 template <bool REG>
-__global__ __launch_bounds__(FP8_QT) void fp8_quant_rows_kernel(
-    const short* __restrict__ X, fp8_t* __restrict__ XQ,
-    float* __restrict__ XS, int K) {
+DEV_INLINE void fp8_quant_row(const short* __restrict__ X,
+                              fp8_t* __restrict__ XQ, float* __restrict__ XS,
+                              int K, size_t row) {
   __shared__ unsigned red[FP8_QT / WAVE];
   const int tid = threadIdx.x, nv = K / 8;
-  const size_t row = blockIdx.x;
   const bf16x8* xr = (const bf16x8*)(X + row * K);
   fp8_t* qr = XQ + row * K;
 
@@ -157,6 +156,26 @@ __global__ __launch_bounds__(FP8_QT) void fp8_quant_rows_kernel(
     for (int j = tid; j < nv; j += FP8_QT)
       fp8_quant8(xr[j], scale, qr + (size_t)j * 8);
   }
+}
+
+template <bool REG>
+__global__ __launch_bounds__(FP8_QT) void fp8_quant_rows_kernel(
+    const short* __restrict__ X, fp8_t* __restrict__ XQ,
+    float* __restrict__ XS, int K) {
+  fp8_quant_row<REG>(X, XQ, XS, K, blockIdx.x);
+}
+
+// The same rows, with the row count on the device: the grid covers the most
+// rows there can be and a block past *ntiles * tile_rows exits (the whole
+// block: the test is uniform, so the barrier inside is safe).  For the MoE
+// lane's h, whose tile count only the align kernel knows (moe_mxfp4.hip).
+template <bool REG>
+__global__ __launch_bounds__(FP8_QT) void fp8_quant_rows_tiles_kernel(
+    const short* __restrict__ X, fp8_t* __restrict__ XQ,
+    float* __restrict__ XS, int K, const int* __restrict__ ntiles,
+    int tile_rows) {
+  if (blockIdx.x >= (unsigned)(*ntiles * tile_rows)) return;
+  fp8_quant_row<REG>(X, XQ, XS, K, blockIdx.x);
 }
 
 // ------------------------------------------------------------------- GEMM
@@ -359,6 +378,28 @@ extern "C" int fp8_quant_rows_bf16(const void* x, void* xq, float* xscale,
     hipLaunchKernelGGL(fp8_quant_rows_kernel<false>, dim3((unsigned)M),
                        dim3(FP8_QT), 0, stream, (const short*)x, (fp8_t*)xq,
                        xscale, K);
+  return 0;
+}
+
+// fp8_quant_rows_bf16 over the first *ntiles * tile_rows rows of x, a count
+// read on the device; max_rows bounds it and sizes the grid.
+extern "C" int fp8_quant_rows_tiles_bf16(const void* x, void* xq,
+                                         float* xscale, long long max_rows,
+                                         int K, const int* ntiles,
+                                         int tile_rows, hipStream_t stream) {
+  if (max_rows < 1 || max_rows >= (1ll << 31) || K < FP8_CH ||
+      K % FP8_CH != 0 || tile_rows < 1)
+    return 1;
+  if (K / 8 <= FP8_QT * FP8_QV)
+    hipLaunchKernelGGL(fp8_quant_rows_tiles_kernel<true>,
+                       dim3((unsigned)max_rows), dim3(FP8_QT), 0, stream,
+                       (const short*)x, (fp8_t*)xq, xscale, K, ntiles,
+                       tile_rows);
+  else
+    hipLaunchKernelGGL(fp8_quant_rows_tiles_kernel<false>,
+                       dim3((unsigned)max_rows), dim3(FP8_QT), 0, stream,
+                       (const short*)x, (fp8_t*)xq, xscale, K, ntiles,
+                       tile_rows);
   return 0;
 }
 

@@ -51,10 +51,8 @@
 // token (moe_route always produces that).  A pair with an id outside [0,E)
 // is skipped by align — its y row is never written — rather than indexed.
 #include "w4_mma.h"  // attention_mfma32.h + the int4 group recipe
+#include "moe_sched.h"  // MOE_BM, MOE_MAX_E, MOE_MAX_K; what moe_mxfp4.hip shares
 
-#define MOE_BM 32          // rows per M-tile = one 32x32 MFMA tile
-#define MOE_MAX_E 128
-#define MOE_MAX_K 8
 #define MOE_ALIGN_NT 1024
 
 // ---------------------------------------------------------------- route
@@ -404,13 +402,36 @@ W4_NO_PK_F32 __global__ __launch_bounds__(256) void moe_combine_planes_kernel(
 // Both return 0 once launched, non-zero (nothing launched) for a
 // configuration outside what the kernels support.
 
-static bool moe_shape_ok(long long N, int E, int top_k) {
+extern "C" int moe_shape_ok(long long N, int E, int top_k) {
   return N >= 1 && E >= 1 && E <= MOE_MAX_E && top_k >= 1 &&
          top_k <= MOE_MAX_K && top_k <= E && N * top_k < (1ll << 30);
 }
 
 extern "C" int moe_max_tiles(long long N, int top_k, int E) {
   return (int)(N * top_k / MOE_BM) + E;
+}
+
+// The two launches every lane shares (moe_sched.h): the schedule into sched's
+// three parts, and the combine over S planes of y.
+extern "C" void moe_align_launch(const int* idx, int P, int E, int max_tiles,
+                                 int* sched, hipStream_t stream) {
+  int* tile_expert = sched + (size_t)max_tiles * MOE_BM;
+  hipLaunchKernelGGL(moe_align_kernel, dim3(1), dim3(MOE_ALIGN_NT), 0, stream,
+                     idx, P, E, sched, tile_expert, tile_expert + max_tiles);
+}
+
+extern "C" void moe_combine_launch(const float* y, const float* weights,
+                                   void* out, long long N, int d, int top_k,
+                                   int S, hipStream_t stream) {
+  const long long n4 = N * (d / 4);
+  int grid = (int)((n4 + 255) / 256 > 4096 ? 4096 : (n4 + 255) / 256);
+  if (S == 1)
+    hipLaunchKernelGGL(moe_combine_kernel, dim3(grid), dim3(256), 0, stream,
+                       y, weights, (short*)out, n4, d / 4, top_k);
+  else
+    hipLaunchKernelGGL(moe_combine_planes_kernel, dim3(grid), dim3(256), 0,
+                       stream, y, weights, (short*)out, n4, d / 4, top_k, S,
+                       N * top_k * d);
 }
 
 extern "C" int moe_route_f32(const float* logits, float* weights, int* idx,
@@ -439,10 +460,7 @@ extern "C" int moe_ffn_bf16(const void* x, const void* gate_up,
   int* slot_map = sched;
   int* tile_expert = sched + (size_t)max_tiles * MOE_BM;
   int* num_tiles = tile_expert + max_tiles;
-  const int P = (int)(N * top_k);
-
-  hipLaunchKernelGGL(moe_align_kernel, dim3(1), dim3(MOE_ALIGN_NT), 0, stream,
-                     idx, P, E, slot_map, tile_expert, num_tiles);
+  moe_align_launch(idx, (int)(N * top_k), E, max_tiles, sched, stream);
   // a 128-deep chunk keeps twice the weight bytes in flight per wave
   if (d % 128 == 0)
     hipLaunchKernelGGL((moe_gemm_kernel<true, 8>), dim3((unsigned)up_blocks),
@@ -468,10 +486,7 @@ extern "C" int moe_ffn_bf16(const void* x, const void* gate_up,
                        (const short*)h, (const short*)down, slot_map,
                        tile_expert, num_tiles, (short*)nullptr, y, F, d,
                        top_k, max_tiles);
-  const long long n4 = N * (d / 4);
-  int grid = (int)((n4 + 255) / 256 > 4096 ? 4096 : (n4 + 255) / 256);
-  hipLaunchKernelGGL(moe_combine_kernel, dim3(grid), dim3(256), 0, stream,
-                     (const float*)y, weights, (short*)out, n4, d / 4, top_k);
+  moe_combine_launch(y, weights, out, N, d, top_k, 1, stream);
   return 0;
 }
 
@@ -523,8 +538,7 @@ extern "C" int moe_ffn_w4_bf16(const void* x, const void* gate_up_q,
   const unsigned short* gus = (const unsigned short*)gate_up_s;
   const unsigned short* ds = (const unsigned short*)down_s;
 
-  hipLaunchKernelGGL(moe_align_kernel, dim3(1), dim3(MOE_ALIGN_NT), 0, stream,
-                     idx, P, E, slot_map, tile_expert, num_tiles);
+  moe_align_launch(idx, P, E, max_tiles, sched, stream);
   hipLaunchKernelGGL((moe_gemm_w4_kernel<true>), dim3((unsigned)up_blocks),
                      dim3(WAVE), 0, stream, (const short*)x, guq, gus,
                      slot_map, tile_expert, num_tiles, (short*)h,
@@ -533,15 +547,6 @@ extern "C" int moe_ffn_w4_bf16(const void* x, const void* gate_up_q,
                      dim3(WAVE), 0, stream, (const short*)h, dq, ds, slot_map,
                      tile_expert, num_tiles, (short*)nullptr, y, F, d, top_k,
                      max_tiles, cps, plane);
-  const long long n4 = N * (d / 4);
-  int grid = (int)((n4 + 255) / 256 > 4096 ? 4096 : (n4 + 255) / 256);
-  if (S == 1)
-    hipLaunchKernelGGL(moe_combine_kernel, dim3(grid), dim3(256), 0, stream,
-                       (const float*)y, weights, (short*)out, n4, d / 4,
-                       top_k);
-  else
-    hipLaunchKernelGGL(moe_combine_planes_kernel, dim3(grid), dim3(256), 0,
-                       stream, (const float*)y, weights, (short*)out, n4,
-                       d / 4, top_k, S, plane);
+  moe_combine_launch(y, weights, out, N, d, top_k, S, stream);
   return 0;
 }

@@ -827,6 +827,123 @@ def moe_ffn_w4(x, gate_up_q, gate_up_s, down_q, down_s, weights, idx):
                           weights.float().contiguous(), idx.contiguous())
 
 
+# ---- MoE FFN over MXFP4 experts.  Format: linear_mxfp4's (below) with a
+# leading expert dimension.  Supported shapes (csrc/moe_mxfp4.hip): moe_ffn's,
+# with dim and ffn_dim multiples of 128.  As above, the checks run on every
+# device before the dispatch.
+
+def quantize_mxfp4_experts(w):
+    """w [E, R, K] (bf16 or fp32) -> (q uint8 [E, R, K/2], s uint8
+    [E, R, K/32]): `quantize_mxfp4` over the flattened rows [E*R, K]."""
+    if w.dim() != 3:
+        raise ValueError(f"w must be [E, R, K], got {tuple(w.shape)}")
+    if not w.is_contiguous():
+        raise ValueError("w must be contiguous")
+    E, R, K = w.shape
+    q, s = quantize_mxfp4(w.view(E * R, K))
+    return q.view(E, R, K // 2), s.view(E, R, K // 32)
+
+
+def _check_mxfp4_experts(name, q, s):
+    """Returns (E, R, K) of a packed expert stack `name`_q / `name`_s."""
+    if q.dtype is not torch.uint8:
+        raise TypeError(f"{name}_q must be uint8, got {q.dtype}")
+    if s.dtype is not torch.uint8:
+        raise TypeError(f"{name}_s must be uint8, got {s.dtype}")
+    if q.dim() != 3 or s.dim() != 3:
+        raise ValueError(f"{name}_q must be [E, R, K/2] and {name}_s "
+                         f"[E, R, K/32], got {tuple(q.shape)}, "
+                         f"{tuple(s.shape)}")
+    E, R, K = q.shape[0], q.shape[1], q.shape[2] * 2
+    if K < 128 or K % 128 != 0:
+        raise ValueError(f"{name}_q has K={K} (must be a multiple of 128)")
+    if tuple(s.shape) != (E, R, K // 32):
+        raise ValueError(f"{name}_s must be [E={E}, R={R}, K/32={K // 32}]"
+                         f", got {tuple(s.shape)}")
+    for n, t in ((f"{name}_q", q), (f"{name}_s", s)):
+        if not t.is_contiguous():
+            raise ValueError(f"{n} must be contiguous")
+        if t.device != q.device:
+            raise ValueError(f"{n} is on {t.device}, {name}_q on {q.device}")
+    return E, R, K
+
+
+def dequantize_mxfp4_experts(q, s):
+    """The dequantized experts w_hat = e2m1(code) * 2^(s - 127), fp32
+    [E, R, K], exact."""
+    _check_mxfp4_experts("w", q, s)
+    return ref.dequantize_mxfp4_experts_ref(q, s)
+
+
+def _check_moe_ffn_mxfp4(x, gate_up_q, gate_up_s, down_q, down_s, weights,
+                         idx):
+    if x.dim() != 2 or x.shape[0] < 1:
+        raise ValueError(f"x must be [N, dim] with N >= 1, got "
+                         f"{tuple(x.shape)}")
+    if not x.is_floating_point():
+        raise TypeError(f"x must be floating point, got {x.dtype}")
+    N, d = x.shape
+    if d < 128 or d % 128 != 0:
+        raise ValueError(f"x has dim={d} (must be a multiple of 128)")
+    E, F2, Kg = _check_mxfp4_experts("gate_up", gate_up_q, gate_up_s)
+    if Kg != d or F2 % 2 != 0:
+        raise ValueError(f"gate_up_q must be [E, 2*ffn_dim, dim/2={d // 2}], "
+                         f"got {tuple(gate_up_q.shape)}")
+    F = F2 // 2
+    if not 1 <= E <= 128:
+        raise ValueError(f"gate_up_q has E={E} experts (supported: 1..128)")
+    if F < 128 or F % 128 != 0:
+        raise ValueError(f"gate_up_q has ffn_dim={F} (must be a multiple of "
+                         f"128)")
+    _check_mxfp4_experts("down", down_q, down_s)
+    if tuple(down_q.shape) != (E, d, F // 2):
+        raise ValueError(f"down_q must be [E={E}, dim={d}, ffn_dim/2="
+                         f"{F // 2}], got {tuple(down_q.shape)}")
+    if idx.dtype is not torch.int32:
+        raise TypeError(f"idx must be int32, got {idx.dtype}")
+    if idx.dim() != 2 or idx.shape[0] != N \
+            or not 1 <= idx.shape[1] <= min(E, 8):
+        raise ValueError(f"idx must be [N={N}, top_k] with top_k in "
+                         f"1..min(E, 8) = {min(E, 8)}, got {tuple(idx.shape)}")
+    if weights.shape != idx.shape:
+        raise ValueError(f"weights must have idx's shape "
+                         f"{tuple(idx.shape)}, got {tuple(weights.shape)}")
+    if not x.is_contiguous():
+        raise ValueError("x must be contiguous")
+    for name, t in (("gate_up_q", gate_up_q), ("gate_up_s", gate_up_s),
+                    ("down_q", down_q), ("down_s", down_s)):
+        if t.device != x.device:
+            raise ValueError(f"{name} is on {t.device}, x on {x.device}")
+
+
+def moe_ffn_mxfp4(x, gate_up_q, gate_up_s, down_q, down_s, weights, idx):
+    """`moe_ffn` over MXFP4 experts (`quantize_mxfp4_experts` of gate_up
+    [E, 2*ffn_dim, dim] and down [E, dim, ffn_dim]) with the activations
+    quantized per row to e4m3 before each GEMM — x once per token, h once
+    per (token, expert) row — which is what a dense Mxfp4Linear SwiGLU FFN
+    computes per expert (`ref.moe_ffn_mxfp4_ref` states the semantics):
+    out[t] = sum_j weights[t, j] * FFN_{idx[t, j]}(x[t]).
+
+    On the GPU in bf16 without grad this is csrc/moe_mxfp4.hip: moe_ffn's
+    schedule, epilogues and combine around grouped GEMMs whose operands are
+    the fp4 bytes, their E8M0 block scales and the e4m3 activations as
+    loaded (the block-scaled MFMA of csrc/linear_mxfp4.hip), with a row
+    quantization pass over h between them.  Same contract as moe_ffn:
+    sync-free, capturable, bitwise reproducible, a token's row independent
+    of the rest of the batch.  Anywhere else it is `ref.moe_ffn_mxfp4_ref`,
+    which is differentiable in x and the routing weights (the roundings pass
+    the gradient straight through).  Scale byte 255 is undefined.  Returns
+    [N, dim] in x's dtype."""
+    _check_moe_ffn_mxfp4(x, gate_up_q, gate_up_s, down_q, down_s, weights,
+                         idx)
+    ext = _ext_for(x, weights)
+    if ext is None:
+        return ref.moe_ffn_mxfp4_ref(x, gate_up_q, gate_up_s, down_q, down_s,
+                                     weights, idx)
+    return ext.moe_ffn_mxfp4(x, gate_up_q, gate_up_s, down_q, down_s,
+                             weights.float().contiguous(), idx.contiguous())
+
+
 # ---- multi-LoRA delta.  Supported shapes (csrc/lora.hip): S <= 32 adapter
 # slots, bank rank R in {16, 32, 64}, K a multiple of 64, O a multiple of 128,
 # any N, contiguous operands.  As above, the checks run on every device

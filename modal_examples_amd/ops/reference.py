@@ -785,6 +785,144 @@ def linear_mxfp4_bound_ref(xq, xscale, qweight, wscale):
     return want, 2.0 ** -7 * want.abs() + 2.0 ** -10 * A
 
 
+# ---- MoE FFN over MXFP4 experts (csrc/moe_mxfp4.hip): the format above with
+# a leading expert dimension, activations quantized per row to e4m3 twice —
+# x once per token, h once per (token, expert) row.
+
+def quantize_mxfp4_experts_ref(w):
+    """w [E, R, K] -> (q uint8 [E, R, K/2], s uint8 [E, R, K/32]):
+    quantize_mxfp4_ref over the flattened rows."""
+    E, R, K = w.shape
+    q, s = quantize_mxfp4_ref(w.reshape(E * R, K))
+    return q.view(E, R, K // 2), s.view(E, R, K // MX_BLOCK)
+
+
+def dequantize_mxfp4_experts_ref(q, s):
+    """w_hat fp32 [E, R, K], exact (dequantize_mxfp4_ref over the flattened
+    rows)."""
+    E, R = q.shape[:2]
+    return dequantize_mxfp4_ref(q.reshape(E * R, -1),
+                                s.reshape(E * R, -1)).view(E, R, -1)
+
+
+def _fp8_rows_through(t, wide):
+    """(q as `wide` [..., K], scale as `wide` [..., 1]) of
+    quantize_rows_fp8_ref(t); the gradient passes the rounding straight
+    through to t, with the scale held constant."""
+    q, scale = quantize_rows_fp8_ref(t)
+    q, scale = q.to(wide), scale.to(wide).unsqueeze(-1)
+    if t.requires_grad:
+        lin = t.to(wide) / scale
+        q = lin + (q - lin).detach()
+    return q, scale
+
+
+def moe_ffn_mxfp4_ref(x, gate_up_q, gate_up_s, down_q, down_s, weights, idx):
+    """The semantics of moe_ffn_mxfp4, dense over the experts like
+    moe_ffn_ref (every expert runs on every token; the routing enters as a
+    coefficient matrix):
+
+      xq, xs = quantize_rows_fp8_ref(x)                  once per token
+      g, u   = xs[t] * (xq[t] . w_hat_gate_up[e]^T)
+      h      = bf16(silu(g) * u)
+      hq, hs = quantize_rows_fp8_ref(h)                  per (token, expert)
+      y      = hs * (hq . w_hat_down[e]^T)
+      out[t] = sum_e coef[t, e] * y[t, e], cast to x's dtype
+
+    in fp32 (fp64 beside an fp64 x) with the exact w_hat.  A row's
+    quantization depends on that row alone, so running an expert on the
+    tokens that are not routed to it changes nothing.  Differentiable in x
+    and the routing weights: the two row quantizations and the bf16 rounding
+    of h pass the gradient straight through."""
+    E, F = gate_up_q.shape[0], down_q.shape[2] * 2
+    wide = _wide(x).dtype
+    xq, xs = _fp8_rows_through(x, wide)
+    coef = torch.zeros(x.shape[0], E, dtype=wide, device=x.device)
+    coef = coef.scatter_add(1, idx.long(), _wide(weights).to(wide))
+    gate_up = dequantize_mxfp4_experts_ref(gate_up_q, gate_up_s).to(wide)
+    down = dequantize_mxfp4_experts_ref(down_q, down_s).to(wide)
+    out = torch.zeros(x.shape, dtype=wide, device=x.device)
+    for e in range(E):
+        gu = (xq @ gate_up[e].T) * xs
+        h = torch.nn.functional.silu(gu[:, :F]) * gu[:, F:]
+        hb = h.detach().to(torch.bfloat16)
+        hq, hs = _fp8_rows_through(hb, wide)
+        if h.requires_grad:
+            lin = h / hs
+            hq = lin + (hq - lin).detach()
+        out = out + coef[:, e:e + 1] * ((hq @ down[e].T) * hs)
+    return out.to(x.dtype)
+
+
+def moe_ffn_mxfp4_bound_ref(x, gate_up_q, gate_up_s, down_q, down_s, weights,
+                            idx, kernel_points=False):
+    """(want, tol) in fp64 on the CPU, [N, dim], for an implementation of
+    moe_ffn_mxfp4_ref that multiplies exact operands, accumulates in fp32
+    and rounds where the semantics say.
+
+      want   fp64 on the quantized x (xq * xs of quantize_rows_fp8_ref, which
+             the row kernel matches bit for bit) and the exact w_hat; h is
+             not rounded.  With w = weights[t, j], e = idx[t, j]:
+             want[t] = sum_j w * (h_e[t] . w_hat_down[e]^T)
+      tol    the sum of the worst cases of the roundings the semantics name:
+
+      2^-7 * |want| + 2^-10 * A_down
+             linear_mxfp4_bound_ref's two terms, for the output's bf16
+             rounding (2^-8, doubled) and the down GEMM's fp32 accumulation,
+             A_down = sum_j w * sum_f |h| * |w_hat_down|.
+      sum_j w * sum_f dh * |w_hat_down|, dh = dh_round + dh_acc
+             what an error dh of every h can move an output by.
+      dh_round = 2^-9 * |h| + max(2^-4 * |h|, 2^-10 * absmax_row / 448)
+             bf16 keeps 8 significant bits: half a step is 2^-9 of the
+             value.  e4m3 keeps 4: half a step is 2^-4 of the value at the
+             bottom of a binade, and below the smallest normal the step is
+             the subnormal one, 2^-9 in units of hscale = absmax_row / 448,
+             half of it 2^-10.
+      dh_acc = 1.1 * 2^-10 * A_gate * |u| + |silu(g)| * 2^-10 * A_up
+             the up GEMM's fp32 accumulation, at most 2^-10 of A_gate =
+             xs * (|xq| . |w_hat_gate|^T) and A_up likewise (K * 2^-24 up
+             to K = 16384), carried through h = silu(g) * u with
+             |silu'| <= 1.1.
+
+    No term is fitted to an implementation's output.  kernel_points=True
+    returns, in place of `want`, the same fp64 pipeline with the roundings
+    applied where the kernel applies them (h to bf16, its row quantization,
+    the output to bf16): the yardstick that shows how much of tol a correct
+    implementation uses."""
+    E, F = gate_up_q.shape[0], down_q.shape[2] * 2
+    xq, xs = quantize_rows_fp8_ref(x.detach().cpu())
+    xd = xq.double() * xs.double().unsqueeze(-1)
+    idx, ww = idx.detach().cpu(), weights.detach().cpu().double()
+    coef = torch.zeros(x.shape[0], E, dtype=torch.float64)
+    coef = coef.scatter_add(1, idx.long(), ww)
+    gate_up = dequantize_mxfp4_experts_ref(gate_up_q.cpu(),
+                                           gate_up_s.cpu()).double()
+    down = dequantize_mxfp4_experts_ref(down_q.cpu(), down_s.cpu()).double()
+    out, outk, tol = (torch.zeros_like(xd) for _ in range(3))
+    for e in range(E):
+        c = coef[:, e:e + 1]
+        gu = xd @ gate_up[e].T
+        A = xd.abs() @ gate_up[e].abs().T
+        g, u = gu[:, :F], gu[:, F:]
+        sg = torch.nn.functional.silu(g)
+        h = sg * u
+        de = down[e]
+        ha = h.abs()
+        floor = 2.0 ** -10 * ha.amax(-1, keepdim=True) / FP8_MAX
+        dh = 2.0 ** -9 * ha + torch.maximum(2.0 ** -4 * ha, floor) \
+            + 2.0 ** -10 * (1.1 * A[:, :F] * u.abs() + sg.abs() * A[:, F:])
+        tol = tol + c.abs() * ((dh + 2.0 ** -10 * ha) @ de.abs().T)
+        out = out + c * (h @ de.T)
+        if kernel_points:
+            hq, hs = quantize_rows_fp8_ref(h.to(torch.bfloat16))
+            hk = hq.double() * hs.double().unsqueeze(-1)
+            outk = outk + c * (hk @ de.T)
+    tol = tol + 2.0 ** -7 * out.abs()
+    if kernel_points:
+        return outk.to(torch.bfloat16).double(), tol
+    return out, tol
+
+
 # ---- multi-LoRA delta (csrc/lora.hip).  bank_a [S, R, K], bank_b [S, O, R]
 # with alpha / r folded into bank_b; idx [N] picks a row's adapter, an id
 # outside [0, S) means "no adapter".

@@ -21,8 +21,15 @@ fused_w4_graph, and dequant_loop_w4, MoEFFN's prefill lane forced at every N
 ops.moe_ffn_w4 with the down GEMM's K forced into 1, 2, 4 and 8 slices,
 beside the shipped rule.
 
+--expert-dtype mxfp4 does the same for the MXFP4-expert lane
+(ops.moe_ffn_mxfp4, csrc/moe_mxfp4.hip): moe_ffn_mxfp4_only, fused_mxfp4,
+fused_mxfp4_graph, dequant_loop_mxfp4 and, with --w4-sweep, mxfp4_only[sS].
+Its yardsticks, moe_ffn_only (bf16) and moe_ffn_w4_only (int4), run in the
+same alternation on the same weights.  Its bytes count 0.53 B per weight
+(4 bits + one E8M0 byte per 32) and the lane's own workspaces (xq, hq).
+
 Usage: python scripts/bench_moe.py [--tokens 64 256 4096] [--e2e]
-                                   [--expert-dtype int4] [--w4-sweep]
+                                   [--expert-dtype int4|mxfp4] [--w4-sweep]
 """
 import argparse
 import os
@@ -70,6 +77,8 @@ def time_arms(arms):
 W4_BYTES = 0.5 + 2 / 128   # per weight: a nibble + a bf16 scale per 128
 W4_DOWN_SLICES = 2         # csrc/moe.hip's rule: min(2, ffn / 128)
 W4_SWEEP = (1, 2, 4, 8)    # K slices of the down GEMM, forced
+MX_BYTES = 0.5 + 1 / 32    # per weight: a nibble + an E8M0 byte per 32
+MX_DOWN_SLICES = 1         # csrc/moe_mxfp4.hip's rule: one slice
 
 
 def ffn_bytes(N, dim, ffn, k, touched, slots, wbytes=2, planes=1):
@@ -94,40 +103,49 @@ def _capture(module, static_x):
     return graph
 
 
-def w4_arms(loop, x, flat, w, idx, sweep):
-    """The int4 arms over loop's weights, quantized; (arms, graph)."""
+def packed_arms(kind, loop, x, flat, w, idx, sweep, only=False):
+    """The arms of packed format `kind` ("w4" or "mxfp4") over loop's
+    weights, quantized; (arms, graph, fused module).  only=True builds the
+    moe_ffn_<kind>_only arm alone (a yardstick for another format's run)."""
     from modal_examples_amd.models.llama.model import MoEFFN
     from modal_examples_amd.ops import functional as OF
     from modal_examples_amd.ops._build import get_ext
 
     E, _, dim = loop.gate_up.shape
     ffn, k = loop.down.shape[2], loop.top_k
-    packed = (OF.quantize_w4_experts(loop.gate_up.data)
-              + OF.quantize_w4_experts(loop.down.data))
+    w4 = kind == "w4"
+    quantize = OF.quantize_w4_experts if w4 else OF.quantize_mxfp4_experts
+    ffn_op = OF.moe_ffn_w4 if w4 else OF.moe_ffn_mxfp4
+    packed = quantize(loop.gate_up.data) + quantize(loop.down.data)
+    arms = {f"moe_ffn_{kind}_only": lambda: ffn_op(flat, *packed, w, idx)}
+    if only:
+        return arms, None, None
+    limit = "N_KERNEL" if w4 else "N_KERNEL_MXFP4"
     mods = []
     for _ in range(2):
         with torch.device("meta"):
-            m = MoEFFN(dim, ffn, E, k, impl="fused", expert_dtype="int4")
+            m = MoEFFN(dim, ffn, E, k, impl="fused",
+                       expert_dtype="int4" if w4 else "mxfp4")
         m.router = loop.router
         m.gate_up_q, m.gate_up_s, m.down_q, m.down_s = packed
         mods.append(m)
-    fused_w4, prefill_w4 = mods
-    fused_w4.N_KERNEL = 1 << 30   # this arm is the kernel lane at every N
-    prefill_w4.N_KERNEL = 0       # and this one the dequantize-and-loop lane
-    graph = _capture(fused_w4, x.clone())
-    arms = {
-        "fused_w4": lambda: fused_w4(x),
-        "fused_w4_graph": graph.replay,
-        "moe_ffn_w4_only": lambda: OF.moe_ffn_w4(flat, *packed, w, idx),
-        "dequant_loop_w4": lambda: prefill_w4(x),
-    }
+    fused_q, prefill_q = mods
+    setattr(fused_q, limit, 1 << 30)  # this arm is the kernel lane at every N
+    setattr(prefill_q, limit, 0)      # and this one the dequantize-and-loop lane
+    graph = _capture(fused_q, x.clone())
+    arms.update({
+        f"fused_{kind}": lambda: fused_q(x),
+        f"fused_{kind}_graph": graph.replay,
+        f"dequant_loop_{kind}": lambda: prefill_q(x),
+    })
     if sweep:
         ext = get_ext(required=True)
+        forced = ext.moe_ffn_w4 if w4 else ext.moe_ffn_mxfp4
         for s in W4_SWEEP:
             if s <= ffn // 128:
-                arms[f"w4_only[s{s}]"] = (
-                    lambda s=s: ext.moe_ffn_w4(flat, *packed, w, idx, s))
-    return arms, graph, fused_w4
+                arms[f"{kind}_only[s{s}]"] = (
+                    lambda s=s: forced(flat, *packed, w, idx, s))
+    return arms, graph, fused_q
 
 
 def bench_ffn(N, dim, ffn, E, k, out, expert_dtype="bf16", sweep=False):
@@ -161,13 +179,18 @@ def bench_ffn(N, dim, ffn, E, k, out, expert_dtype="bf16", sweep=False):
             "moe_ffn_only": lambda: OF.moe_ffn(flat, loop.gate_up, loop.down,
                                                w, idx),
         }
-        if expert_dtype == "int4":
-            more, graph_w4, fused_w4 = w4_arms(loop, x, flat, w, idx, sweep)
+        kind = {"int4": "w4", "mxfp4": "mxfp4"}.get(expert_dtype)
+        if kind == "mxfp4":  # the int4 kernel lane is a yardstick here
+            arms.update(packed_arms("w4", loop, x, flat, w, idx, False,
+                                    only=True)[0])
+        if kind:
+            more, graph_q, fused_q = packed_arms(kind, loop, x, flat, w, idx,
+                                                 sweep)
             arms.update(more)
         res = time_arms(arms)
         diff = (fused(x).float() - loop(x).float()).abs().max().item()
-        if expert_dtype == "int4":
-            diff_w4 = (fused_w4(x).float() - fused(x).float()).abs().max().item()
+        if kind:
+            diff_q = (fused_q(x).float() - fused(x).float()).abs().max().item()
     counts = torch.bincount(idx.flatten().long(), minlength=E)
     touched = int((counts > 0).sum())
     slots = int(((counts + 31) // 32 * 32).sum())
@@ -184,23 +207,36 @@ def bench_ffn(N, dim, ffn, E, k, out, expert_dtype="bf16", sweep=False):
         f"{(wb + ob) / t / 1e12 / HBM_COPY_TBS:.0%} of the {HBM_COPY_TBS} TB/s"
         f" copy rate (memory bound: {2 * 3 * N * k * dim * ffn / t / 1e12:.0f}"
         f" TFLOP/s is far below the MFMA peak)")
-    if expert_dtype == "int4":
-        a, b = res["moe_ffn_w4_only"], res["moe_ffn_only"]
-        t4 = a[0] * 1e-6
-        planes = min(W4_DOWN_SLICES, ffn // 128)
-        wb4, ob4 = ffn_bytes(N, dim, ffn, k, touched, slots, W4_BYTES, planes)
-        out(f"N={N:5d} int4/bf16 moe_ffn_only = {a[0] / b[0]:.3f} "
-            f"({b[0] / a[0]:.2f}x; spreads: int4 {a[2] - a[1]:.1f} us, bf16 "
-            f"{b[2] - b[1]:.1f} us, gap {b[0] - a[0]:.1f} us)   "
-            f"max|fused_w4-fused| = {diff_w4:.3e} (quantization included)")
-        out(f"N={N:5d} moe_ffn_w4_only: {wb4 / 1e6:.1f} MB weights + "
-            f"{ob4 / 1e6:.1f} MB activations/workspaces -> "
-            f"{(wb4 + ob4) / t4 / 1e12:.2f} TB/s algorithmic = "
-            f"{(wb4 + ob4) / t4 / 1e12 / HBM_COPY_TBS:.0%} of the "
+    if kind:
+        a, b = res[f"moe_ffn_{kind}_only"], res["moe_ffn_only"]
+        tq = a[0] * 1e-6
+        if kind == "w4":
+            planes = min(W4_DOWN_SLICES, ffn // 128)
+            wbq, obq = ffn_bytes(N, dim, ffn, k, touched, slots, W4_BYTES,
+                                 planes)
+        else:
+            planes = min(MX_DOWN_SLICES, ffn // 128)
+            wbq, obq = ffn_bytes(N, dim, ffn, k, touched, slots, MX_BYTES,
+                                 planes)
+            # xq written once, read by every up tile row; hq written and read
+            obq += 2 * N * dim + 2 * slots * ffn
+        out(f"N={N:5d} {expert_dtype}/bf16 moe_ffn_only = {a[0] / b[0]:.3f} "
+            f"({b[0] / a[0]:.2f}x; spreads: {expert_dtype} {a[2] - a[1]:.1f} "
+            f"us, bf16 {b[2] - b[1]:.1f} us, gap {b[0] - a[0]:.1f} us)   "
+            f"max|fused_{kind}-fused| = {diff_q:.3e} (quantization included)")
+        if kind == "mxfp4":
+            c = res["moe_ffn_w4_only"]
+            out(f"N={N:5d} mxfp4/int4 moe_ffn_only = {a[0] / c[0]:.3f} "
+                f"({c[0] / a[0]:.2f}x; spreads: mxfp4 {a[2] - a[1]:.1f} us, "
+                f"int4 {c[2] - c[1]:.1f} us, gap {c[0] - a[0]:.1f} us)")
+        out(f"N={N:5d} moe_ffn_{kind}_only: {wbq / 1e6:.1f} MB weights + "
+            f"{obq / 1e6:.1f} MB activations/workspaces -> "
+            f"{(wbq + obq) / tq / 1e12:.2f} TB/s algorithmic = "
+            f"{(wbq + obq) / tq / 1e12 / HBM_COPY_TBS:.0%} of the "
             f"{HBM_COPY_TBS} TB/s copy rate")
-        out(f"N={N:5d} crossover: kernel lane {res['fused_w4'][0]:.1f} us, "
-            f"dequantize-and-loop lane {res['dequant_loop_w4'][0]:.1f} us")
-        del graph_w4
+        out(f"N={N:5d} crossover: kernel lane {res[f'fused_{kind}'][0]:.1f} us, "
+            f"dequantize-and-loop lane {res[f'dequant_loop_{kind}'][0]:.1f} us")
+        del graph_q
     del graph
 
 
@@ -210,8 +246,8 @@ def bench_e2e(out, layers=8, batch=64, steps=24, expert_dtype="bf16"):
 
     lanes = [("loop", False, "bf16"), ("fused", False, "bf16"),
              ("fused", True, "bf16")]
-    if expert_dtype == "int4":
-        lanes += [("fused", False, "int4"), ("fused", True, "int4")]
+    if expert_dtype != "bf16":
+        lanes += [("fused", False, expert_dtype), ("fused", True, expert_dtype)]
     for impl, graph, edt in lanes:
         torch.manual_seed(0)
         cfg = LlamaConfig(n_experts=8, ffn_dim=4096, n_layers=layers)
@@ -248,7 +284,8 @@ def main():
     ap.add_argument("--experts", type=int, default=8)
     ap.add_argument("--top-k", type=int, default=2)
     ap.add_argument("--e2e", action="store_true")
-    ap.add_argument("--expert-dtype", choices=("bf16", "int4"), default="bf16")
+    ap.add_argument("--expert-dtype", choices=("bf16", "int4", "mxfp4"),
+                    default="bf16")
     ap.add_argument("--w4-sweep", action="store_true")
     ap.add_argument("--out", default=None, help="also append the lines here")
     a = ap.parse_args()

@@ -97,6 +97,12 @@ OCCUPANCY_FLOORS = {
     "mxfp4_gemm_kernelILi1E": 2,
     "mxfp4_gemm_kernelILi2E": 2,
     "mxfp4_reduce_kernel": 8,
+    # moe_gemm_mxfp4_kernel<UP>: mxfp4_gemm_kernel<1>'s picture (two sets of
+    # 34 registers, 32 accumulators) plus the slot-map gather and the expert
+    # base; built for four waves per SIMD (128 registers)
+    "moe_gemm_mxfp4_kernelILb1E": 4,   # up GEMM
+    "moe_gemm_mxfp4_kernelILb0E": 4,   # down GEMM, one K slice per wave
+    "fp8_quant_rows_tiles_kernel": 8,  # the row quantizer, device row count
 }
 
 
