@@ -81,8 +81,10 @@ void cfg_euler_dev_bf16(const void*, const void*, const void*, void*,
 void advance_step(long long*, hipStream_t);
 void conv3x3_bf16(const void*, const void*, const void*, const void*,
                   const void*, void*, const float*, const float*, float*, int,
-                  int, int, int, int, int, int, int, hipStream_t);
-void conv3x3_stats_dims(int, int, int, int*, int*);
+                  int, int, int, int, int, int, int, int, hipStream_t);
+int conv3x3_tile_rule(int, int, int, int, int, int, int);
+int conv3x3_tile_rpw(int, int, int, int, int, int, int);
+void conv3x3_stats_dims(int, int, int, int, int*, int*);
 void gn_conv_coeffs_bf16(const void*, float*, const float*, const float*,
                          float*, float*, int, int, int, long long, int, float,
                          int, hipStream_t);
@@ -862,6 +864,11 @@ ConvDims check_conv(const char* op, const torch::Tensor& x,
 // the second result, [N, gn_groups, 2] f32 (sum, sumsq), is what
 // groupnorm_silu* and conv3x3_gn accept as `stats`.  The output itself is
 // that of the call without.
+//
+// The tile (rows per wave) is decided once per call, by conv3x3_tile_rpw, and
+// handed to everything that depends on it: the partials' workspace, the
+// launcher and the finalize kernel.  With statistics the third result is that
+// workspace, [N, npix, nquads, 2] f32.
 std::vector<torch::Tensor> conv3x3_impl(
     torch::Tensor x, torch::Tensor wr, torch::Tensor bias,
     c10::optional<torch::Tensor> residual, int64_t K, bool upsample,
@@ -879,13 +886,15 @@ std::vector<torch::Tensor> conv3x3_impl(
                 addend->sizes());
   }
   auto out = torch::empty({d.N, K, d.Ho, d.Wo}, x.options());
+  const int rpw = conv3x3_tile_rpw((int)d.N, (int)d.C, (int)d.Ho, (int)d.Wo,
+                                   (int)K, upsample ? 1 : 0, 0);
   torch::Tensor part;
   int npix = 0, nquads = 0;
   if (gn_groups > 0) {
     TORCH_CHECK(K % gn_groups == 0 && (K / gn_groups) % 4 == 0,
                 "conv3x3: statistics need gn_groups that divide K into a "
                 "multiple of 4 channels, got gn_groups=", gn_groups, " K=", K);
-    conv3x3_stats_dims(d.Ho, d.Wo, (int)K, &npix, &nquads);
+    conv3x3_stats_dims(rpw, d.Ho, d.Wo, (int)K, &npix, &nquads);
     TORCH_CHECK((int64_t)npix * (K / gn_groups / 4) < (1ll << 31) &&
                     d.N * gn_groups < (1ll << 29),
                 "conv3x3: too large for the statistics kernels, got x ",
@@ -898,7 +907,7 @@ std::vector<torch::Tensor> conv3x3_impl(
                addend.has_value() ? addend->data_ptr() : nullptr,
                out.data_ptr(), nullptr, nullptr,
                gn_groups > 0 ? part.data_ptr<float>() : nullptr, d.N, d.C,
-               d.Ho, d.Wo, (int)K, d.C16, d.Kpad, upsample ? 1 : 0,
+               d.Ho, d.Wo, (int)K, d.C16, d.Kpad, upsample ? 1 : 0, rpw,
                cur_stream());
   if (gn_groups <= 0) return {out};
   // every slot is written: no zero fill
@@ -907,7 +916,7 @@ std::vector<torch::Tensor> conv3x3_impl(
   gn_stats_finalize(part.data_ptr<float>(), sums.data_ptr<float>(), d.N,
                     (int)gn_groups, (int)(K / gn_groups / 4), npix, nquads,
                     cur_stream());
-  return {out, sums};
+  return {out, sums, part};
 }
 
 torch::Tensor conv3x3(torch::Tensor x, torch::Tensor wr, torch::Tensor bias,
@@ -922,7 +931,35 @@ std::vector<torch::Tensor> conv3x3_stats(
     c10::optional<torch::Tensor> addend, int64_t gn_groups) {
   TORCH_CHECK(gn_groups >= 1, "conv3x3: gn_groups must be at least 1, got ",
               gn_groups);
+  auto r = conv3x3_impl(x, wr, bias, residual, K, upsample, addend, gn_groups);
+  return {r[0], r[1]};
+}
+
+// conv3x3_stats plus the per-block partials the sums were finalized from.
+std::vector<torch::Tensor> conv3x3_stats_partials(
+    torch::Tensor x, torch::Tensor wr, torch::Tensor bias,
+    c10::optional<torch::Tensor> residual, int64_t K, bool upsample,
+    c10::optional<torch::Tensor> addend, int64_t gn_groups) {
+  TORCH_CHECK(gn_groups >= 1, "conv3x3: gn_groups must be at least 1, got ",
+              gn_groups);
   return conv3x3_impl(x, wr, bias, residual, K, upsample, addend, gn_groups);
+}
+
+// (rows per wave, npix, nquads) of a call of this shape in this process; H, W
+// are the output's, gn says conv3x3_gn.  rule_only leaves MODAL_AMD_CONV_RPW
+// out.
+std::vector<int64_t> conv3x3_tile(int64_t N, int64_t C, int64_t H, int64_t W,
+                                  int64_t K, bool upsample, bool gn,
+                                  bool rule_only) {
+  TORCH_CHECK(N >= 1 && C >= 1 && H >= 1 && W >= 1 && K >= 1 &&
+                  N < (1ll << 31) && C < (1ll << 31) && H < (1ll << 31) &&
+                  W < (1ll << 31) && K < (1ll << 31),
+              "conv3x3_tile: sizes must be positive 32-bit values");
+  const int rpw = (rule_only ? conv3x3_tile_rule : conv3x3_tile_rpw)(
+      (int)N, (int)C, (int)H, (int)W, (int)K, upsample ? 1 : 0, gn ? 1 : 0);
+  int npix = 0, nquads = 0;
+  conv3x3_stats_dims(rpw, (int)H, (int)W, (int)K, &npix, &nquads);
+  return {rpw, npix, nquads};
 }
 
 // GroupNorm+SiLU fused INTO the conv's staging read: one stats pass over x,
@@ -953,11 +990,13 @@ torch::Tensor conv3x3_gn(torch::Tensor x, torch::Tensor wr, torch::Tensor bias,
                       C16, HW, (int)groups, (float)eps,
                       stats.has_value() ? 1 : 0, cur_stream());
   auto out = torch::empty({N, K, d.Ho, d.Wo}, x.options());
+  const int rpw = conv3x3_tile_rpw(N, (int)d.C, (int)d.Ho, (int)d.Wo, (int)K,
+                                   upsample ? 1 : 0, 1);
   conv3x3_bf16(x.data_ptr(), wr.data_ptr(), bias.data_ptr(),
                residual.has_value() ? residual->data_ptr() : nullptr,
                nullptr, out.data_ptr(), scale.data_ptr<float>(),
                shift.data_ptr<float>(), nullptr, N, d.C, d.Ho, d.Wo, (int)K,
-               C16, d.Kpad, upsample ? 1 : 0, cur_stream());
+               C16, d.Kpad, upsample ? 1 : 0, rpw, cur_stream());
   return out;
 }
 
@@ -1764,6 +1803,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("x"), py::arg("wr"), py::arg("bias"), py::arg("residual"),
         py::arg("K"), py::arg("upsample"), py::arg("addend"),
         py::arg("gn_groups"));
+  m.def("conv3x3_stats_partials", &conv3x3_stats_partials,
+        "conv3x3_stats and, third, the per-block partials "
+        "[N, npix, nquads, 2] the sums were finalized from",
+        py::arg("x"), py::arg("wr"), py::arg("bias"), py::arg("residual"),
+        py::arg("K"), py::arg("upsample"), py::arg("addend"),
+        py::arg("gn_groups"));
+  m.def("conv3x3_tile", &conv3x3_tile,
+        "(rows per wave, npix, nquads) of a conv3x3 call of this shape: the "
+        "tile rule, or with rule_only=False what MODAL_AMD_CONV_RPW forces",
+        py::arg("N"), py::arg("C"), py::arg("H"), py::arg("W"), py::arg("K"),
+        py::arg("upsample") = false, py::arg("gn") = false,
+        py::arg("rule_only") = false);
   m.def("conv3x3_gn", &conv3x3_gn, "GroupNorm+SiLU fused into the K3 conv",
         py::arg("x"), py::arg("wr"), py::arg("bias"), py::arg("residual"),
         py::arg("K"), py::arg("upsample"), py::arg("gamma"), py::arg("beta"),

@@ -8,20 +8,26 @@
 // LDS during staging.
 //
 // Formulation: 9 shifted GEMMs.  out[k][p] = sum_tap sum_c W[tap][k][c] *
-// in[c][p+tap].  M = 64 out-channels, N = 256 pixels (8 rows x 32 cols),
-// K-dim = C in chunks of 16 (mfma_f32_32x32x16_bf16).
+// in[c][p+tap].  M = 64 out-channels, N = 256 or 512 pixels (8 or 16 rows x
+// 32 cols, chosen per call: conv3x3_tile_rule), K-dim = C in chunks of 16
+// (mfma_f32_32x32x16_bf16).
 //
-//  - Input patch staged per 16-channel chunk as LDS [10 rows][34 cols][16 c]
+//  - Input patch staged per 16-channel chunk as LDS [rows+2][34 cols][16 c]
 //    (c innermost): the MFMA B-fragment read (8 consecutive c at the lane's
 //    pixel) is one ds_read_b128 at 32 B col-stride -> 64 lanes cover a
 //    contiguous span, every bank hit evenly (conflict-free; guide §6 G4
 //    applies to same-column strides, not contiguous spans).
-//  - Weights repacked on host to [9][Kpad][C16] (c contiguous) so the MFMA
-//    A-fragment is one bf16x8 global read; per-k-tile weight working set
-//    (64 x C x 9 x 2B <= 590 KB) stays L2-resident across the XCD-chunked
-//    run of pixel tiles (bijective chunk swizzle, guide §5 T1/m204).
-//  - Wave w owns output rows {2w, 2w+1} and BOTH 32-k fragments: 36 MFMA per
-//    18 ds_read_b128 per chunk (2:1, the m97 GEMM ratio).
+//  - Weights repacked on host to [9][Kpad][C16] (c contiguous).  The block
+//    stages the chunk's [9][64][16] tile into LDS once (one bf16x8 global
+//    read per slot, shared by the four waves) and the MFMA A-fragment is one
+//    ds_read_b128 from it; per-k-tile weight working set (64 x C x 9 x 2B
+//    <= 590 KB) stays L2-resident across the XCD-chunked run of pixel tiles
+//    (bijective chunk swizzle, guide §5 T1/m204).
+//  - Wave w owns RPW output rows and BOTH 32-k fragments.  Per chunk it
+//    reads 18 weight fragments (9 taps x 2) and 3 * (RPW + 2) input
+//    fragments - each patch row x column offset once, shared by the taps
+//    that use it -: RPW = 2 runs 36 MFMA per 30 ds_read_b128 (1.2:1),
+//    RPW = 4 runs 72 per 36 (2:1).
 //  - Staging is software-pipelined: chunk cc+1's input and weight loads
 //    issue back to back right after chunk cc's second barrier and are first
 //    waited for after chunk cc's last MFMA.  Every input load is
@@ -92,8 +98,10 @@ DEV_INLINE int to_sgpr(int v) {
 }
 
 // RPW = output rows per wave (block rows = CV_NW*RPW).  RPW=2 runs 3
-// waves/SIMD (its register budget: __launch_bounds__ below); RPW=4 doubles
-// MFMA per staged byte/A-read at 1 wave/SIMD (128 accumulator registers).
+// waves/SIMD (64 accumulators in a 168-register budget); RPW=4 doubles the
+// MFMAs per staged byte and per weight read at 2 waves/SIMD: 128 accumulators
+// and everything else within 256 registers, every MFMA in its VGPR form (the
+// budgets: __launch_bounds__ below, held by check_kernel_resources.py).
 // LDS patch: [rows+2][CV_COLS+2][CV_CC] bf16, c innermost.
 #define PATCH_C (CV_COLS + 2)
 
@@ -112,7 +120,7 @@ DEV_INLINE int to_sgpr(int v) {
 // with per-(n,c) coefficients from gn_conv_coeffs_bf16 (norms.hip).  The
 // gn_norm write+read pass over the full tensor disappears.
 template <bool UP, bool GN, int RPW>
-__global__ __launch_bounds__(CV_NW * WAVE, RPW == 2 ? 3 : 1)
+__global__ __launch_bounds__(CV_NW * WAVE, RPW == 2 ? 3 : 2)
 void conv3x3_kernel(
     const short* __restrict__ in, const short* __restrict__ wr,
     const float* __restrict__ bias, const short* __restrict__ res,
@@ -334,19 +342,30 @@ void conv3x3_kernel(
     // one base per operand; every tap/row is a compile-time LDS offset
     const short* wl = &wlds[l31 * CV_CC + hi5 * 8];
     const short* pl = &patch[(w * RPW * PATCH_C + l31) * CV_CC + hi5 * 8];
+    // dx outer, then a window of RPW patch rows that slides down by one per
+    // dy: the B-fragment of tap (dy, dx) for output row rr is patch row
+    // rr + dy at column offset dx, so every fragment is read ONCE and feeds
+    // each (row, k-fragment) MFMA that uses it - 3 * (RPW + 2) input reads
+    // per chunk instead of 9 * RPW, beside the 18 weight reads.  Live at a
+    // time: the two A-fragments of one tap and RPW B-fragments.
 #pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-      const int dy = tap / 3, dx = tap - 3 * (tap / 3);
-      bf16x8 a0 = *(const bf16x8*)&wl[tap * CV_BK * CV_CC];
-      bf16x8 a1 = *(const bf16x8*)&wl[(tap * CV_BK + 32) * CV_CC];
+    for (int dx = 0; dx < 3; ++dx) {
+      bf16x8 b[RPW + 2];
 #pragma unroll
-      for (int rr = 0; rr < RPW; ++rr) {
-        bf16x8 b =
-            *(const bf16x8*)&pl[((rr + dy) * PATCH_C + dx) * CV_CC];
-        __builtin_amdgcn_s_setprio(1);
-        acc[rr][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b, acc[rr][0], 0, 0, 0);
-        acc[rr][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b, acc[rr][1], 0, 0, 0);
-        __builtin_amdgcn_s_setprio(0);
+      for (int dy = 0; dy < 3; ++dy) {
+        const int tap = dy * 3 + dx;
+        bf16x8 a0 = *(const bf16x8*)&wl[tap * CV_BK * CV_CC];
+        bf16x8 a1 = *(const bf16x8*)&wl[(tap * CV_BK + 32) * CV_CC];
+#pragma unroll
+        for (int rr = 0; rr < RPW; ++rr) {
+          const int pr = rr + dy;  // patch row
+          if (dy == 0 || rr == RPW - 1)
+            b[pr] = *(const bf16x8*)&pl[(pr * PATCH_C + dx) * CV_CC];
+          __builtin_amdgcn_s_setprio(1);
+          acc[rr][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a0, b[pr], acc[rr][0], 0, 0, 0);
+          acc[rr][1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1, b[pr], acc[rr][1], 0, 0, 0);
+          __builtin_amdgcn_s_setprio(0);
+        }
       }
     }
   }
@@ -511,35 +530,69 @@ void conv3x3_kernel(
   else dispatch(no);
 }
 
-static int conv_rpw() {
-  // rows-per-wave A/B (MODAL_AMD_CONV_RPW=4): doubles MFMA per staged
-  // byte/A-read at 1 wave/SIMD occupancy.
-  static const int rpw = [] {
-    const char* e = getenv("MODAL_AMD_CONV_RPW");
-    return (e && atoi(e) == 4) ? 4 : 2;
-  }();
-  return rpw;
+// Blocks of a call at `rpw` rows per wave (grid x * y).
+static long long conv_blocks(int rpw, int N, int H, int W, int K) {
+  const int rows = CV_NW * rpw;
+  return (long long)((W + CV_COLS - 1) / CV_COLS) * ((H + rows - 1) / rows) *
+         ((K + CV_BK - 1) / CV_BK) * N;
 }
 
-// The statistics workspace of an H x W x K output: [N][npix][nquads][2] f32.
-extern "C" void conv3x3_stats_dims(int H, int W, int K, int* npix,
+// The tile rule: rows per wave (2: 8-row tile, 4: 16-row tile) as a pure
+// function of the call's shape; H, W are the OUTPUT dims.  PERF.md, "conv3x3:
+// input fragments shared between taps, 16-row tile per call", has the table
+// it rests on.
+extern "C" int conv3x3_tile_rule(int N, int C, int H, int W, int K,
+                                 int upsample, int gn) {
+  (void)upsample;  // both upsample shapes of the table fall on the same side
+  // GroupNorm in the staging: not timed with the 16-row tile, stays at 8
+  if (gn) return 2;
+  // a few chunks only: the block is mostly epilogue and gains nothing from
+  // fewer LDS reads per MFMA (4 -> 512 @128^2: no faster, +res slower)
+  if (C < 128) return 2;
+  // the 16-row tiling may round H up by 8 rows more than the 8-row tiling:
+  // taken only where those are no rows at all or under 1/16 of the image
+  const int rows16 = (H + 15) / 16 * 16, rows8 = (H + 7) / 8 * 8;
+  if (rows16 != rows8 && H < 128) return 2;
+  // two blocks of the 16-row tile are resident per CU, 512 on the 256 CUs:
+  // faster from two such rounds of blocks on (1024: 512 -> 512 @128^2 x 4),
+  // level at 640 blocks, slower at 320 and 160
+  return conv_blocks(4, N, H, W, K) >= 2 * 2 * 256 ? 4 : 2;
+}
+
+// The tile of one call: the rule, or MODAL_AMD_CONV_RPW=2|4 (read once per
+// process) for A/B runs.  The launcher, conv3x3_stats_dims and the caller of
+// gn_stats_finalize all take the value this returns.
+extern "C" int conv3x3_tile_rpw(int N, int C, int H, int W, int K,
+                                int upsample, int gn) {
+  static const int forced = [] {
+    const char* e = getenv("MODAL_AMD_CONV_RPW");
+    const int v = e ? atoi(e) : 0;
+    return (v == 2 || v == 4) ? v : 0;
+  }();
+  return forced ? forced : conv3x3_tile_rule(N, C, H, W, K, upsample, gn);
+}
+
+// The statistics workspace of an H x W x K output written at `rpw` rows per
+// wave: [N][npix][nquads][2] f32.
+extern "C" void conv3x3_stats_dims(int rpw, int H, int W, int K, int* npix,
                                    int* nquads) {
-  const int rows = CV_NW * conv_rpw();
+  const int rows = CV_NW * rpw;
   *npix = ((W + CV_COLS - 1) / CV_COLS) * ((H + rows - 1) / rows);
   *nquads = ((K + CV_BK - 1) / CV_BK) * (CV_BK / 4);
 }
 
+// rpw: conv3x3_tile_rpw() of this call (the caller sized `stats` from it).
 extern "C" void conv3x3_bf16(const void* in, const void* wrepack,
                              const void* bias, const void* residual,
                              const void* addend, void* out,
                              const float* gn_scale, const float* gn_shift,
                              float* stats, int N, int C, int H, int W, int K,
                              int C16,
-                             int Kpad, int upsample, hipStream_t stream) {
+                             int Kpad, int upsample, int rpw,
+                             hipStream_t stream) {
   // H/W are the OUTPUT dims; with upsample the source is H/2 x W/2.
   const int Hs = upsample ? H / 2 : H;
   const int Ws = upsample ? W / 2 : W;
-  const int rpw = conv_rpw();
   const int rows = CV_NW * rpw;
   const int npix_x = (W + CV_COLS - 1) / CV_COLS;
   const int npix_y = (H + rows - 1) / rows;

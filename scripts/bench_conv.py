@@ -73,10 +73,12 @@ def timeit_span(fn, span=0.25, warmup=3):
     return timeit(fn, iters=max(10, int(span / one) + 1), warmup=0)
 
 
-def kernel_exp(miopen=True):
+def kernel_exp(miopen=True, only=None, batch=None):
     """Hand conv3x3 kernel (K3) per hot shape: plain, with the fused residual
     add, and the fused-upsample variant; TF rate of the plain call and, with
-    `miopen`, the MIOpen NCHW time beside it.  Every figure spans >= 0.2 s."""
+    `miopen`, the MIOpen NCHW time beside it.  Every figure spans >= 0.2 s.
+    `only`: indices into the shape list (--shapes 0,2,7), for counter runs;
+    `batch` (--batch B) replaces the list's B = 4."""
     import math
 
     from modal_examples_amd.gpu import kernel_cache
@@ -96,6 +98,10 @@ def kernel_exp(miopen=True):
         (4, 256, 256, 1024, 1024, True),   # VAE upsample convs: the source
         (4, 512, 512, 256, 256, True),     # is half the output size
     ]
+    if only is not None:
+        shapes = [shapes[i] for i in only]
+    if batch is not None:  # the tile rule counts blocks, so it depends on B
+        shapes = [(batch,) + s[1:] for s in shapes]
     print(f"{'shape':30s} {'miopen':>8s} {'hand':>8s} {'hand+res':>9s} "
           f"{'speedup':>8s} {'TF':>6s}")
     tot_mi = tot_hand = tot_res = 0.0
@@ -136,7 +142,15 @@ if __name__ == "__main__":
     import sys as _sys
 
     if "--kernel" in _sys.argv:
-        kernel_exp(miopen="--no-miopen" not in _sys.argv)
+        only = None
+        if "--shapes" in _sys.argv:
+            only = [int(i) for i in
+                    _sys.argv[_sys.argv.index("--shapes") + 1].split(",")]
+        batch = None
+        if "--batch" in _sys.argv:
+            batch = int(_sys.argv[_sys.argv.index("--batch") + 1])
+        kernel_exp(miopen="--no-miopen" not in _sys.argv, only=only,
+                   batch=batch)
     else:
         conv_exp()
         gemm_exp()

@@ -47,11 +47,13 @@ OCCUPANCY_FLOORS = {
     "conv3x3_kernelILb1ELb0ELi2E": 3,
     "conv3x3_kernelILb0ELb1ELi2E": 3,
     "conv3x3_kernelILb1ELb1ELi2E": 3,
-    # conv3x3_kernel<UP, GN, RPW=4>: 128 accumulators, one wave per SIMD
-    "conv3x3_kernelILb0ELb0ELi4E": 1,
-    "conv3x3_kernelILb1ELb0ELi4E": 1,
-    "conv3x3_kernelILb0ELb1ELi4E": 1,
-    "conv3x3_kernelILb1ELb1ELi4E": 1,
+    # conv3x3_kernel<UP, GN, RPW=4>: 128 accumulators and the rest of the
+    # 16-row tile's state within 256 registers, two waves per SIMD (38 KB of
+    # LDS per block: two blocks per CU)
+    "conv3x3_kernelILb0ELb0ELi4E": 2,
+    "conv3x3_kernelILb1ELb0ELi4E": 2,
+    "conv3x3_kernelILb0ELb1ELi4E": 2,
+    "conv3x3_kernelILb1ELb1ELi4E": 2,
     # one block per (image, group) sums the conv epilogue's quad partials
     "gn_stats_finalize_kernel": 8,
     "gn_partial_kernel": 8,
