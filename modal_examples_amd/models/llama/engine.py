@@ -164,8 +164,10 @@ class LlamaEngine:
         (ops.quantize_fp8; model.Fp8Linear), 1 byte per weight, and
         quantizes the activations per token at run time: batches up to
         Fp8Linear.M_KERNEL rows run on the csrc/linear_fp8.hip kernels
-        inside the decode graph, larger ones dequantize into a scratch
-        weight.  Everything else said for "int4" (what stays in `dtype`,
+        inside the decode graph, larger ones (prefill) on the same file's
+        workgroup-tiled fp8 GEMM with the same per-token quantization
+        (Fp8Linear.PREFILL_LANE = "tiled"; "dequant" restores the scratch
+        bf16 weight and the ordinary GEMM).  Everything else said for "int4" (what stays in `dtype`,
         quantization before the KV pool is sized, init_weights=False, tp,
         MoE configs) holds for it unchanged.  "mxfp4" holds them as OCP MX
         fp4: two e2m1 codes a byte with one E8M0 scale byte per 32 inputs

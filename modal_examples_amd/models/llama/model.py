@@ -138,12 +138,17 @@ class Fp8Linear(nn.Module):
     Two lanes, as QuantLinear.  Up to M_KERNEL rows the forward is
     ops.linear_fp8: on the GPU the row-quantization kernel and the fp8 MFMA
     GEMM of csrc/linear_fp8.hip, which multiply the fp8 values exactly and
-    apply both scales to the fp32 sum.  Above that the weight is dequantized
-    into a scratch tensor of the activation dtype and goes through the
-    ordinary GEMM on the unquantized activations; in bf16 that rounds every
-    w_hat = wscale * q to bf16 and skips the activation quantization, so the
-    two lanes differ by those roundings.  On the CPU, in fp32 or under
-    autograd, the kernel lane is the reference composition."""
+    apply both scales to the fp32 sum.  Above that, PREFILL_LANE picks.
+    "tiled" (on the GPU in bf16 without grad): ops.linear_fp8(tiled=True),
+    the same row quantizer and the workgroup-tiled fp8 GEMM of the same
+    file, so a token's projection is the same arithmetic in prefill and in
+    decode and no weight-sized scratch is made.  "dequant" (and "tiled"
+    anywhere else): the weight is dequantized into a scratch tensor of the
+    activation dtype and goes through the ordinary GEMM on the unquantized
+    activations; in bf16 that rounds every w_hat = wscale * q to bf16 and
+    skips the activation quantization, so it differs from the kernel lanes
+    by those roundings.  On the CPU, in fp32 or under autograd, the kernel
+    lane is the reference composition."""
 
     # rows up to which the kernel lane is taken.  Measured
     # (profiles/linear_fp8.txt, second table, "fp8" against "fp8deq"): at
@@ -153,6 +158,17 @@ class Fp8Linear(nn.Module):
     # (273 / 179, 204 / 127, 962 / 898, 508 / 491 us).  1024 is the largest
     # measured count on the kernel's side of the crossover.
     M_KERNEL = 1024
+
+    # the lane above M_KERNEL rows on the GPU in bf16 without grad: "tiled"
+    # (ops.linear_fp8(tiled=True)) or "dequant".  Measured
+    # (profiles/linear_fp8_tiled.txt, "fp8tile" against the faster of "fp8"
+    # and "fp8deq" in the same windows): the tiled lane wins on all four
+    # Llama-3-8B projections at 2048, 4096 and 8192 rows (2048: 89 / 180,
+    # 58 / 129, 343 / 901, 178 / 488 us; 8192, the narrowest: 298 / 381,
+    # 206 / 246, 1304 / 1822, 671 / 876 us), against a spread of under 1 %
+    # between the windows of either arm.  The M_KERNEL figures above are from
+    # the earlier table and have not moved with this lane.
+    PREFILL_LANE = "tiled"
 
     def __init__(self, in_features: int, out_features: int, device=None):
         super().__init__()
@@ -198,6 +214,13 @@ class Fp8Linear(nn.Module):
         rows = x.numel() // self.in_features
         if rows <= self.M_KERNEL:
             return OF.linear_fp8(x, self.qweight, self.wscale)
+        if self.PREFILL_LANE not in ("tiled", "dequant"):
+            raise ValueError(f"Fp8Linear.PREFILL_LANE={self.PREFILL_LANE!r} "
+                             f"(must be 'tiled' or 'dequant')")
+        if (self.PREFILL_LANE == "tiled" and x.is_cuda
+                and x.dtype is torch.bfloat16
+                and not (torch.is_grad_enabled() and x.requires_grad)):
+            return OF.linear_fp8(x, self.qweight, self.wscale, tiled=True)
         w = OF.dequantize_fp8(self.qweight, self.wscale).to(x.dtype)
         return nn.functional.linear(x, w)
 

@@ -124,6 +124,9 @@ int fp8_quant_rows_bf16(const void*, void*, float*, long long, int,
 int linear_fp8_bf16(const void*, const float*, const void*, const float*,
                     float*, void*, long long, int, int, int, int,
                     hipStream_t);
+int linear_fp8_tiled_bf16(const void*, const float*, const void*,
+                          const float*, void*, long long, int, int, int,
+                          hipStream_t);
 // linear_mxfp4_plan / linear_mxfp4_bf16: as the fp8 pair, with u8 [N,K/2]
 // weights and u8 [N,K/32] E8M0 block scales
 int linear_mxfp4_plan(long long, int, int, int);
@@ -1335,13 +1338,12 @@ std::vector<torch::Tensor> quantize_rows_fp8(torch::Tensor x) {
   return {xq, xscale};
 }
 
-// xq fp8 [M,K], xscale fp32 [M], qweight fp8 [N,K], wscale fp32 [N].
-// splits = 0 takes the kernel's split rule and mtiles = 0 its M-tile rule;
-// positive values force them (tests and benchmarks only — the public op
-// never passes them).  Returns [M,N] bf16.
-torch::Tensor linear_fp8(torch::Tensor xq, torch::Tensor xscale,
-                         torch::Tensor qweight, torch::Tensor wscale,
-                         int64_t splits, int64_t mtiles) {
+// The operand checks of linear_fp8 and linear_fp8_tiled, one set of messages.
+// Clones an operand the kernels could not read as 16 B fragments.
+static void check_linear_fp8_operands(torch::Tensor& xq,
+                                      torch::Tensor& xscale,
+                                      torch::Tensor& qweight,
+                                      torch::Tensor& wscale) {
   for (const auto* t : {&xq, &qweight})
     TORCH_CHECK(t->is_cuda() && t->is_contiguous() &&
                     t->scalar_type() == torch::kFloat8_e4m3fn,
@@ -1371,14 +1373,26 @@ torch::Tensor linear_fp8(torch::Tensor xq, torch::Tensor xscale,
                   xscale.device() == xq.device() &&
                   wscale.device() == xq.device(),
               "linear_fp8: all tensors must be on xq's device");
-  TORCH_CHECK(M < (1ll << 31) && N < (1ll << 31) && K < (1ll << 31) &&
-                  splits >= 0 && splits < (1ll << 31) && mtiles >= 0 &&
-                  mtiles <= 2,
+  TORCH_CHECK(M < (1ll << 31) && N < (1ll << 31) && K < (1ll << 31),
               "linear_fp8: size out of range");
   // the kernels read 16 B fragments
   if ((uintptr_t)xq.data_ptr() % 16) xq = xq.clone();
   if ((uintptr_t)qweight.data_ptr() % 16) qweight = qweight.clone();
   if ((uintptr_t)wscale.data_ptr() % 16) wscale = wscale.clone();
+}
+
+// xq fp8 [M,K], xscale fp32 [M], qweight fp8 [N,K], wscale fp32 [N].
+// splits = 0 takes the kernel's split rule and mtiles = 0 its M-tile rule;
+// positive values force them (tests and benchmarks only — the public op
+// never passes them).  Returns [M,N] bf16.
+torch::Tensor linear_fp8(torch::Tensor xq, torch::Tensor xscale,
+                         torch::Tensor qweight, torch::Tensor wscale,
+                         int64_t splits, int64_t mtiles) {
+  check_linear_fp8_operands(xq, xscale, qweight, wscale);
+  const int64_t M = xq.size(0), K = xq.size(1), N = qweight.size(0);
+  TORCH_CHECK(splits >= 0 && splits < (1ll << 31) && mtiles >= 0 &&
+                  mtiles <= 2,
+              "linear_fp8: size out of range");
   const int S = linear_fp8_plan(M, (int)N, (int)K, (int)splits);
   TORCH_CHECK(S >= 1, "linear_fp8: shape not supported by the kernel (M=", M,
               " N=", N, " K=", K, " splits=", splits, ")");
@@ -1392,6 +1406,25 @@ torch::Tensor linear_fp8(torch::Tensor xq, torch::Tensor xscale,
                            (int)mtiles, cur_stream());
   TORCH_CHECK(rc == 0, "linear_fp8: shape not supported by the kernel (M=", M,
               " N=", N, " K=", K, " splits=", splits, ")");
+  return out;
+}
+
+// linear_fp8's operands through the workgroup-tiled kernel (prefill sizes).
+// tile = 0 takes the kernel's tile rule; 1 / 2 force the 128x128 / 256x128
+// tile (tests and benchmarks only).  Returns [M,N] bf16.
+torch::Tensor linear_fp8_tiled(torch::Tensor xq, torch::Tensor xscale,
+                               torch::Tensor qweight, torch::Tensor wscale,
+                               int64_t tile) {
+  check_linear_fp8_operands(xq, xscale, qweight, wscale);
+  const int64_t M = xq.size(0), K = xq.size(1), N = qweight.size(0);
+  TORCH_CHECK(tile >= 0 && tile <= 2, "linear_fp8: size out of range");
+  auto out = torch::empty({M, N}, xq.options().dtype(torch::kBFloat16));
+  int rc = linear_fp8_tiled_bf16(xq.data_ptr(), xscale.data_ptr<float>(),
+                                 qweight.data_ptr(),
+                                 wscale.data_ptr<float>(), out.data_ptr(), M,
+                                 (int)N, (int)K, (int)tile, cur_stream());
+  TORCH_CHECK(rc == 0, "linear_fp8: shape not supported by the kernel (M=", M,
+              " N=", N, " K=", K, " tile=", tile, ")");
   return out;
 }
 
@@ -1852,6 +1885,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         "fp8 W8A8 linear: fp8 MFMA on the loaded bytes, split-K",
         py::arg("xq"), py::arg("xscale"), py::arg("qweight"),
         py::arg("wscale"), py::arg("splits") = 0, py::arg("mtiles") = 0);
+  m.def("linear_fp8_tiled", &linear_fp8_tiled,
+        "fp8 W8A8 linear for prefill: LDS-tiled fp8 MFMA GEMM, no split-K",
+        py::arg("xq"), py::arg("xscale"), py::arg("qweight"),
+        py::arg("wscale"), py::arg("tile") = 0);
   m.def("linear_fp8_splits", &linear_fp8_splits,
         "K slices linear_fp8 uses for (M, N, K); 0 = unsupported shape",
         py::arg("M"), py::arg("N"), py::arg("K"), py::arg("splits") = 0);

@@ -1207,12 +1207,13 @@ def quantize_rows_fp8(x):
     return xq.view(x.shape), xs.view(x.shape[:-1])
 
 
-def linear_fp8_q(xq, xscale, qweight, wscale):
+def linear_fp8_q(xq, xscale, qweight, wscale, tiled=False):
     """The GEMM of `linear_fp8` alone: xq float8_e4m3fn [M, K] with xscale
     fp32 [M] (quantize_rows_fp8) against qweight / wscale (quantize_fp8),
     y[m, n] = bf16((sum_k xq[m,k] * qweight[n,k]) * xscale[m] * wscale[n]),
-    [M, N] bf16.  On the GPU fp8_gemm_kernel; elsewhere the same arithmetic
-    in torch ops."""
+    [M, N] bf16.  On the GPU fp8_gemm_kernel, or with tiled=True the
+    workgroup-tiled fp8_gemm_tiled_kernel built for prefill-sized M;
+    elsewhere the same arithmetic in torch ops."""
     N, K = _check_fp8_weight(qweight, wscale)
     if xq.dtype is not torch.float8_e4m3fn:
         raise TypeError(f"xq must be float8_e4m3fn, got {xq.dtype}")
@@ -1233,11 +1234,11 @@ def linear_fp8_q(xq, xscale, qweight, wscale):
     if not xq.is_cuda:
         return ref.linear_fp8_q_ref(xq, xscale, qweight, wscale)
     ext = _sync_wrapped(get_ext(required=True))
-    return ext.linear_fp8(xq.contiguous(), xscale.contiguous(), qweight,
-                          wscale)
+    gemm = ext.linear_fp8_tiled if tiled else ext.linear_fp8
+    return gemm(xq.contiguous(), xscale.contiguous(), qweight, wscale)
 
 
-def linear_fp8(x, qweight, wscale):
+def linear_fp8(x, qweight, wscale, tiled=False):
     """x [..., K] . w_hat^T with fp8 weights (quantize_fp8) and x quantized
     per row at run time ("W8A8 dynamic"), K2f.
 
@@ -1246,16 +1247,21 @@ def linear_fp8(x, qweight, wscale):
     loaded, the two scales multiply the fp32 sum, one rounding to bf16; K is
     split deterministically, the result of a row is bitwise reproducible
     and independent of the other rows, and the call captures into a graph.
+    tiled=True takes the same row quantizer and then the workgroup-tiled
+    GEMM (fp8_gemm_tiled_kernel: operands staged through LDS and shared by
+    four waves, no split-K), built for prefill-sized row counts; the
+    arithmetic contract and the guarantees are the same.
     Anywhere else it is the reference composition on the same device
-    (quantize rows, dequantize both, `linear`).  Returns [..., N] in x's
-    dtype."""
+    (quantize rows, dequantize both, `linear`), whatever `tiled` says.
+    Returns [..., N] in x's dtype."""
     N, K = _check_fp8_weight(qweight, wscale)
     _check_fp8_x(x, K, qweight)
     ext = _ext_for(x)
     if ext is None:
         return ref.linear_fp8_ref(x, qweight, wscale)
     xq, xs = ext.quantize_rows_fp8(x.reshape(-1, K).contiguous())
-    y = ext.linear_fp8(xq, xs, qweight, wscale)
+    gemm = ext.linear_fp8_tiled if tiled else ext.linear_fp8
+    y = gemm(xq, xs, qweight, wscale)
     return y.view(*x.shape[:-1], N)
 
 

@@ -21,13 +21,20 @@ dequantize-then-GEMM lane of Fp8Linear.  With --sweep it also times the fp8
 GEMM under forced split counts (M = 1, 32) and with one against two M-tiles
 per wave (M >= 64).
 
+--fp8-tiled is --fp8 plus the workgroup-tiled prefill GEMM
+(fp8_gemm_tiled_kernel), meant for --rows 256 .. 8192: "fp8tile", the public
+op ops.linear_fp8(tiled=True) under the tile rule; "fp8tile1" / "fp8tile2",
+the same two launches with the 128x128 / 256x128 tile forced; "fp8tilegemm",
+the GEMM alone.  "parent/fp8tile" is the faster of "fp8" and "fp8deq" (the
+two lanes Fp8Linear had before) over "fp8tile".
+
 --mxfp4 adds the MXFP4 arms (csrc/linear_mxfp4.hip) in the same way:
 "mxfp4", the public op ops.linear_mxfp4; "mxfp4gemm", the GEMM alone;
 "mxfp4deq", the dequantize-then-GEMM lane of Mxfp4Linear; with --sweep the
 GEMM under forced split counts and with one against two M-tiles per wave.
 
 Usage: python scripts/bench_linear_w4.py [--rows 1 8 32] [--sweep] [--fp8]
-                                         [--mxfp4] [--out F]
+                                         [--fp8-tiled] [--mxfp4] [--out F]
 """
 import argparse
 import os
@@ -96,7 +103,7 @@ def time_graphs(graphs):
             for n, s in samples.items()}
 
 
-def fp8_arms(ext, OF, name, N, K, M, x, fq, fs, sweep, out):
+def fp8_arms(ext, OF, name, N, K, M, x, fq, fs, sweep, out, tiled=False):
     """The fp8 graphs of one (shape, M), and the sweep lines."""
     Rf = len(fq)
     xq, xs = OF.quantize_rows_fp8(x)
@@ -105,12 +112,25 @@ def fp8_arms(ext, OF, name, N, K, M, x, fq, fs, sweep, out):
         w = OF.dequantize_fp8(fq[i], fs[i]).to(torch.bfloat16)
         return torch.nn.functional.linear(x, w)
 
+    def tile(t):
+        def call(i):
+            return ext.linear_fp8_tiled(*ext.quantize_rows_fp8(x), fq[i],
+                                        fs[i], t)
+        return call
+
     graphs = {
         "fp8": (capture(lambda i: OF.linear_fp8(x, fq[i], fs[i]), Rf), Rf),
         "fp8gemm": (capture(
             lambda i: ext.linear_fp8(xq, xs, fq[i], fs[i]), Rf), Rf),
         "fp8deq": (capture(deq, 2), 2),
     }
+    if tiled:
+        graphs["fp8tile"] = (capture(
+            lambda i: OF.linear_fp8(x, fq[i], fs[i], tiled=True), Rf), Rf)
+        graphs["fp8tile1"] = (capture(tile(1), Rf), Rf)
+        graphs["fp8tile2"] = (capture(tile(2), Rf), Rf)
+        graphs["fp8tilegemm"] = (capture(
+            lambda i: ext.linear_fp8_tiled(xq, xs, fq[i], fs[i]), Rf), Rf)
     if not sweep:
         return graphs
     if M in (1, 32):
@@ -174,7 +194,8 @@ def mxfp4_arms(ext, OF, name, N, K, M, x, mq, ms, sweep, out):
     return graphs
 
 
-def bench_shape(name, N, K, rows, sweep, out, fp8=False, mxfp4=False):
+def bench_shape(name, N, K, rows, sweep, out, fp8=False, mxfp4=False,
+                tiled=False):
     from modal_examples_amd.ops import functional as OF
     from modal_examples_amd.ops._build import get_ext
 
@@ -224,7 +245,7 @@ def bench_shape(name, N, K, rows, sweep, out, fp8=False, mxfp4=False):
             }
             if fp8:
                 graphs.update(fp8_arms(ext, OF, name, N, K, M, x, fq, fs,
-                                       sweep, out))
+                                       sweep, out, tiled))
             if mxfp4:
                 graphs.update(mxfp4_arms(ext, OF, name, N, K, M, x, mq, ms,
                                          sweep, out))
@@ -242,6 +263,11 @@ def bench_shape(name, N, K, rows, sweep, out, fp8=False, mxfp4=False):
             if fp8:
                 line += (f" bf16/fp8 {res['bf16'][0] / res['fp8'][0]:.2f}x"
                          f" w4/fp8 {res['w4'][0] / res['fp8'][0]:.2f}x")
+            if tiled:
+                parent = min(res["fp8"][0], res["fp8deq"][0])
+                line += (f" parent/fp8tile {parent / res['fp8tile'][0]:.2f}x"
+                         f" bf16/fp8tile "
+                         f"{res['bf16'][0] / res['fp8tile'][0]:.2f}x")
             if mxfp4:
                 line += (f" bf16/mxfp4 {res['bf16'][0] / res['mxfp4'][0]:.2f}x"
                          f" w4/mxfp4 {res['w4'][0] / res['mxfp4'][0]:.2f}x")
@@ -276,6 +302,8 @@ def main():
     ap.add_argument("--shapes", nargs="+", default=[s[0] for s in SHAPES])
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--fp8", action="store_true")
+    ap.add_argument("--fp8-tiled", action="store_true",
+                    help="--fp8 plus the tiled prefill arms")
     ap.add_argument("--mxfp4", action="store_true")
     ap.add_argument("--out", default=None, help="also append the lines here")
     a = ap.parse_args()
@@ -293,7 +321,8 @@ def main():
         f">= {ROTATE_BYTES >> 20} MB; GB/s = the arm's weight bytes / time")
     for name, N, K in SHAPES:
         if name in a.shapes:
-            bench_shape(name, N, K, a.rows, a.sweep, out, a.fp8, a.mxfp4)
+            bench_shape(name, N, K, a.rows, a.sweep, out,
+                        a.fp8 or a.fp8_tiled, a.mxfp4, a.fp8_tiled)
 
 
 if __name__ == "__main__":

@@ -90,6 +90,14 @@ OCCUPANCY_FLOORS = {
     # per SIMD, the second hides a chunk's load latency as in w4_gemm_kernel
     "fp8_gemm_kernelILi1E": 2,
     "fp8_gemm_kernelILi2E": 2,
+    # fp8_gemm_tiled_kernel<WM>: WM x 2 C fragments (64 / 128 accumulators
+    # for WM = 2 / 4) beside one chunk of staged loads in flight (12 / 16
+    # registers x 4) and the LDS operands of a half chunk.  WM = 2 (128x128,
+    # 64 KB of LDS) is built for two workgroups per CU, two waves per SIMD
+    # (176 VGPRs + 64 AGPRs); WM = 4 (256x128, 96 KB) fits one workgroup
+    # per CU and one wave per SIMD
+    "fp8_gemm_tiled_kernelILi2E": 2,
+    "fp8_gemm_tiled_kernelILi4E": 1,
     "fp8_reduce_kernel": 8,
     "fp8_quant_rows_kernel": 8,   # both: row in registers, row read twice
     # mxfp4_gemm_kernel<MT>: two register sets of a 128-deep chunk (34 / 50
